@@ -1,8 +1,14 @@
 """Benchmark: lego NeRF training rays/s (forward + backward, 64 coarse + 128 fine samples).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps of the headline dtype and prints the line.
+``--full`` adds everything else described below (the other MLP dtypes, the renders and the
+occupancy grid, the per-kernel detail steps, the eager and the CPU baseline).
+``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy (float32);
+the inputs are seeded, so two builds run with the same arguments can be compared array by array.
 
 A step is one full training step of the reference hot path on one GPU's batch:
 4096 random rays (GPU ray generation from a 100-view 800x800 synthetic lego-shaped scene)
@@ -13,8 +19,9 @@ Weights: the reference's seed-0 init (torch.manual_seed(0); Network()).  Data is
 synthetic (no dataset offline).  Rank 0 prints one JSON line.
 
 The headline (``value``, ``dtype`` "fp32") runs the MLP in fp32 MFMA, the reference's own
-precision (nn.Linear fp32, network.py:22-74).  Three opt-in MLP precisions are measured in the
-same run and reported as nested, labelled lines: ``bf16x3_line`` (split-bf16 operands, three
+precision (nn.Linear fp32, network.py:22-74).  With ``--full`` three opt-in MLP precisions are
+measured in the same run and reported as nested, labelled lines:
+``bf16x3_line`` (split-bf16 operands, three
 bf16 MFMAs per product, ~1e-5 relative per dot product; priced against 1/3 of the bf16 peak),
 ``bf16x3f_line`` (the bf16x3 forward -- its rgb/depth are bf16x3's -- with the bf16 backward)
 and ``bf16_line`` (operands rounded to bf16: the non-conforming tier, rgb/depth within the north_star's
@@ -85,7 +92,19 @@ def parse(argv=None):
     ap.add_argument("--cpu-rays", type=int, default=1024)
     ap.add_argument("--detail-steps", type=int, default=5,
                     help="extra untimed steps that time the sampling/compositing kernels (after the timed region)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the other MLP dtypes, the 800x800 renders and "
+                         "the occupancy grid, the per-kernel detail steps, the eager PyTorch-ROCm and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline dtype returned as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        args.no_second = args.no_render = args.no_cpu_baseline = args.no_eager_baseline = True
+        args.detail_steps = 0
+    return args
 
 
 def free_port() -> int:
@@ -288,6 +307,32 @@ def hbm_roofline(k, n, ms, dtype, samples=None):
             "frac": round(ach / PEAK_HBM_GBS, 4), "traffic_source": src}
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, last, opt):
+    """What the last timed step handed its caller, one float32 ``<name>.npy`` each: the render's
+    tensors (``out_<key>``), the losses, and the state the step leaves behind in the optimizer's
+    flat buffers (``grad``: the step's gradient, ``params``: the weights after its update).  An
+    array larger than its share of DUMP_MAX_BYTES is cut to a seed-0 sample of its flat entries
+    (sorted indices, the same from run to run)."""
+    import numpy as np
+    output, loss, loss_stats = last
+    arrays = {f"out_{k}": v for k, v in output.items() if torch.is_tensor(v)}
+    arrays["loss"] = loss
+    arrays.update({k: v for k, v in loss_stats.items() if torch.is_tensor(v)})
+    arrays["grad"], arrays["params"] = opt.flat_grad, opt.flat_param
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays) // 4
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name.replace("/", "_") + ".npy"), np.ascontiguousarray(a))
+    log(f"wrote {len(arrays)} arrays to {path}")
+
+
 def measure_training(args, world, rank, device, dtype):
     """Warmup + exactly args.steps timed steps (barrier + synchronize on both sides, max over
     ranks).  Returns (rays/s, ms/step, roofline, per-kernel table, train-size stream kernels,
@@ -303,13 +348,17 @@ def measure_training(args, world, rank, device, dtype):
     ops.KERNEL_TIMES.reset()
     ops.KERNEL_TIMES.enabled = True
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        train_step(cfg, trainer, opt, ds, device)
+    for i in range(args.steps):
+        last = train_step(cfg, trainer, opt, ds, device)
+        if i + 1 < args.steps:
+            last = None  # a step's outputs (and what their graph holds) go before the next step starts
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     ops.KERNEL_TIMES.enabled = False
+    if args.dump_outputs and rank == 0 and dtype == args.dtype:
+        dump_outputs(args.dump_outputs, last, opt)
     dist_info = None
     if world > 1:
         per_rank = gather_floats(elapsed / args.steps * 1e3, device)

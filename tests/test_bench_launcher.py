@@ -81,3 +81,37 @@ def test_torchrun_two_ranks_env():
         os.remove(prog)
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout.strip() == '{"world": "2", "local": "0", "addr": "127.0.0.1"}'
+
+
+def test_plain_run_measures_only_the_headline(bench):
+    """Without --full the options that add work beside the timed steps are all off, whatever else is
+    given; with --full they are what the command line says."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_second and a.no_render and a.no_cpu_baseline and a.no_eager_baseline and a.detail_steps == 0
+    a = bench.parse(["--steps", "7", "--detail-steps", "3", "--dump-outputs", "d"])
+    assert a.detail_steps == 0 and a.dump_outputs == "d"
+    a = bench.parse(["--full"])
+    assert not (a.no_second or a.no_render or a.no_cpu_baseline or a.no_eager_baseline) and a.detail_steps == 5
+    a = bench.parse(["--full", "--no-render", "--detail-steps", "2"])
+    assert a.no_render and not a.no_second and a.detail_steps == 2
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_large_array_is_sampled(bench, tmp_path, monkeypatch):
+    """An array beyond its share of the budget is cut to a fixed sample (CPU tensors suffice)."""
+    import numpy as np
+    import torch
+
+    class Opt:
+        flat_grad = torch.arange(1000, dtype=torch.float32)
+        flat_param = torch.zeros(10)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 4 * 100)  # 4 arrays, 100 values each
+    last = ({"rgb": torch.ones(5, 3)}, torch.tensor(1.0), {})
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), last, Opt)
+    g = np.load(tmp_path / "a" / "grad.npy")
+    assert g.shape == (100,) and (np.diff(g) > 0).all()
+    assert (g == np.load(tmp_path / "b" / "grad.npy")).all()
+    assert np.load(tmp_path / "a" / "out_rgb.npy").shape == (5, 3)

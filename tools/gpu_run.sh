@@ -5,7 +5,7 @@
 #   tests=EXPR       -m gpu tests selected by -k EXPR (+ for spaces)
 #   file=PATH        -m gpu tests of one file
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (python bench.py)
+#   bench            the whole bench line, every tier and baseline (python bench.py --full)
 #   benchq           a short bench (10 steps, no CPU / eager baselines)
 #   nrank=N          bench.py --gpus N on this one GPU (gloo rehearsal of the launcher path)
 #   rccl1            the RCCL (nccl backend) collective path at world size 1
@@ -42,16 +42,16 @@ for step in "$@"; do
     tests=*) nm=$((nm + 1)); k=${step#tests=}; run "tests_k$nm" 900 $PYT --maxfail=10 tests -k "${k//+/ }" ;;
     file=*) f=${step#file=}; run "file_$(basename $f .py)" 900 $PYT --maxfail=10 "$f" ;;
     smoke) run smoke 180 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ;;
-    bench) run bench 600 python3 -u bench.py ;;
-    benchq) run benchq 400 python3 -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-eager-baseline ;;
-    nrank=*) n=${step#nrank=}; NERF_BENCH_BACKEND=gloo run "nrank$n" 700 python3 -u bench.py --gpus "$n" --steps 3 --warmup 1 ;;
+    bench) run bench 600 python3 -u bench.py --full ;;
+    benchq) run benchq 400 python3 -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-eager-baseline ;;
+    nrank=*) n=${step#nrank=}; NERF_BENCH_BACKEND=gloo run "nrank$n" 700 python3 -u bench.py --full --gpus "$n" --steps 3 --warmup 1 ;;
     rccl1) run rccl1 200 python3 -u tools/rccl_probe.py ;;
     prof) rm -rf gpurun_out/prof
           run prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o bench --output-format csv -- \
-            python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-eager-baseline ;;
+            python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-eager-baseline ;;
     pmc=*) run "pmc_${step#pmc=}" 900 bash tools/gpu_pmc_mlp.sh "${step#pmc=}" ;;
     traffic=*) dt=${step#traffic=}; rm -rf gpurun_out/tr_$dt
-          B="python3 bench.py --dtype $dt --no-second --no-render --no-cpu-baseline --no-eager-baseline --steps 3 --warmup 1 --detail-steps 2"
+          B="python3 bench.py --full --dtype $dt --no-second --no-render --no-cpu-baseline --no-eager-baseline --steps 3 --warmup 1 --detail-steps 2"
           run "trF_$dt" 300 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/tr_$dt/F -o p --output-format csv -- $B
           run "trW_$dt" 300 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/tr_$dt/W -o p --output-format csv -- $B
           python3 tools/pmc_traffic.py gpurun_out/tr_$dt/F/p_counter_collection.csv gpurun_out/tr_$dt/W/p_counter_collection.csv $dt > gpurun_out/traffic_$dt.json || exit 1 ;;

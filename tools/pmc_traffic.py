@@ -1,7 +1,7 @@
 """Per-launch HBM traffic of the MLP, sampling and compositing kernels from rocprofv3 --pmc CSVs.
 
-    rocprofv3 --pmc FETCH_SIZE -d <dir_f> -o fetch --output-format csv -- python3 bench.py ...
-    rocprofv3 --pmc WRITE_SIZE -d <dir_w> -o write --output-format csv -- python3 bench.py ...
+    rocprofv3 --pmc FETCH_SIZE -d <dir_f> -o fetch --output-format csv -- python3 bench.py --full ...
+    rocprofv3 --pmc WRITE_SIZE -d <dir_w> -o write --output-format csv -- python3 bench.py --full ...
     python tools/pmc_traffic.py <fetch csv> <write csv> bf16 > profiles/rN/traffic.json
 
 FETCH_SIZE / WRITE_SIZE are in KiB.  On gfx950 FETCH_SIZE reports half the bytes of a
