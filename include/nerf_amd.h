@@ -228,6 +228,43 @@ int nerf_march_composite(const float* raw, const float* rays, int64_t N, const f
                          float t_thresh, unsigned long long* consumed, hipStream_t stream);
 int nerf_march_finish(float* rgb, const float* acc, int64_t N, int white, hipStream_t stream);
 
+/* ---- (a12) under autograd: render_accelerated with a graph back to the fine net ------------------
+ * The reference's march is plain torch (volume_renderer.py:268-357), so its maps differentiate when
+ * autograd is on.  Here that is two passes.  Pass A is the march above, without gradient, through
+ * nerf_march_composite_used = nerf_march_composite that also adds each ray's points composited this
+ * round to ray_used[N] (nullable; zero it first): the steps the reference queries for that ray
+ * (:307-324), early termination (:341) included.  Pass B differentiates through exactly those points:
+ * seg_off[N+1] = the exclusive prefix sum of ray_used (int32, built by the caller on the device), so
+ * ray r owns the positions [seg_off[r], seg_off[r+1]) -- ray order, no atomics, the same layout run
+ * to run.
+ *
+ * nerf_march_segments: walks every ray from step 0 with the gather's exact empty-space skip and
+ * writes its first seg_off[r+1] - seg_off[r] occupied steps (ray id, step, point o + t d; :303-312)
+ * at seg_off[r]; a ray with fewer occupied steps gets step -1, its own id and its origin in the
+ * surplus positions.  Every position in [0, seg_off[N]) is written.  n_steps < 65536.
+ *
+ * nerf_march_seg_composite_fwd / _bwd: the accumulation of :327-339 and :349-351 over each segment,
+ * with no termination test (every point of a segment is used), and its backward w.r.t. raw [M,4]
+ * (M = seg_off[N]); the sigmoid / ReLU of :329-330 included.  A point with out_step < 0 has weight 0
+ * and a zero gradient row; every row of g_raw is written; g_rgb / g_depth / g_acc may be null (= 0).
+ * Deterministic (one wave per ray, scans across the lanes, no atomics); division-free, so
+ * alpha = 1 gives zero gradients after it, never 0/0. */
+int nerf_march_composite_used(const float* raw, const float* rays, int64_t N, const float* t_table,
+                              const int32_t* ray_off, const int32_t* ray_cnt, const int32_t* out_step, float* T,
+                              float* rgb, float* depth, float* acc, int32_t* next_step, uint8_t* alive,
+                              uint8_t* exhausted, float step_size, float t_thresh, unsigned long long* consumed,
+                              int32_t* ray_used, hipStream_t stream);
+int nerf_march_segments(const float* rays, int64_t N, const float* t_table, int n_steps, const uint8_t* grid, int res,
+                        const uint8_t* macro, const float* bbox_host, const int32_t* seg_off, int32_t* out_ray,
+                        int32_t* out_step, float* out_pts, hipStream_t stream);
+int nerf_march_seg_composite_fwd(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                 const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                 float* rgb, float* depth, float* acc, hipStream_t stream);
+int nerf_march_seg_composite_bwd(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                 const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                 const float* g_rgb, const float* g_depth, const float* g_acc, float* g_raw,
+                                 hipStream_t stream);
+
 /* ---- (a10) clip_grad_value_ + Adam (src/train/trainers/trainer.py:61-62, optimizer.py:8-28) ---- */
 int nerf_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
                    double beta2, double eps, int64_t step, double clip_value, hipStream_t stream);

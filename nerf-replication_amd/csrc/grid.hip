@@ -461,6 +461,7 @@ struct MarchCompArgs {
   MarchState st;
   float step_size, t_thresh;
   unsigned long long* consumed;  // += points composited (the reference's MLP queries) or null
+  int32_t* ray_used;             // [N] += this ray's points composited this round, or null
 };
 
 __device__ __forceinline__ int march_composite_ray_impl(const MarchCompArgs& a, int64_t r);
@@ -477,6 +478,7 @@ __global__ void march_composite_kernel(MarchCompArgs a) {
   const bool live = r < a.N && a.st.alive[r];
   int used = 0;
   if (live) used = march_composite_ray(a, r);
+  if (a.ray_used && live) a.ray_used[r] += used;
   if (a.consumed) {
     // wave-aggregated count
     int tot = used;
@@ -559,6 +561,239 @@ __global__ void march_finish_kernel(MarchFinishArgs a) {
   const float bg = fsub(1.f, a.st.acc[r]);  // rgb += (1 - acc) * 1
 #pragma unroll
   for (int k = 0; k < 3; ++k) a.st.rgb[r * 3 + k] = fadd(a.st.rgb[r * 3 + k], bg);
+}
+
+// ------------------------------------------------------------------------------------
+// differentiable march: per-ray segments (the training step through the grid)
+// ------------------------------------------------------------------------------------
+// The march above decides, without gradient, how many points each ray composites (ray_used).
+// The three kernels below run the differentiable pass over exactly those points: every ray's
+// points laid out contiguously in ray order (segment r = [seg_off[r], seg_off[r+1]), the
+// exclusive prefix sum of the counts -- no atomic reservation, so the sample order, and with it
+// the dW sum order, is the same run to run), composited with no termination test.
+
+// One thread per ray: the gather's walk from step 0 (same skips, same points), the ray's first
+// seg_off[r+1] - seg_off[r] occupied steps written at seg_off[r].  A ray with fewer occupied
+// steps than its count gets step -1 and its origin in the surplus positions.
+__global__ void march_segments_kernel(MarchGatherArgs a, const int32_t* seg_off) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.N) return;
+  const int64_t pos = seg_off[r];
+  const int64_t cnt = (int64_t)seg_off[r + 1] - pos;
+  const float* ray = a.rays + r * 6;
+  int64_t k = 0;
+  int s = 0;
+  float p[3];
+  int cell[3];
+  while (s < a.n_steps && k < cnt) {
+    if (march_occupied(a, ray, a.t_table[s], p, cell)) {
+      march_put(a, r, ray, pos + k, s);
+      ++k;
+      ++s;
+    } else {
+      s = march_next_after_empty(a, ray, s, cell);
+    }
+  }
+  for (; k < cnt; ++k) {
+    a.out_ray[pos + k] = (int32_t)r;
+    a.out_step[pos + k] = -1;
+    a.out_pts[(pos + k) * 3 + 0] = ray[0];
+    a.out_pts[(pos + k) * 3 + 1] = ray[1];
+    a.out_pts[(pos + k) * 3 + 2] = ray[2];
+  }
+}
+
+struct SegCompArgs {
+  const float* raw;  // [M,4]
+  const float* rays;
+  int64_t N;
+  const float* t_table;
+  const int32_t* seg_off;   // [N+1]
+  const int32_t* out_step;  // [M] (< 0: a surplus point, weight 0)
+  float step_size;
+  int white;
+  float* rgb;    // forward outputs
+  float* depth;
+  float* acc;
+  const float* g_rgb;  // backward inputs (each nullable = 0)
+  const float* g_depth;
+  const float* g_acc;
+  float* g_raw;  // [M,4]
+};
+
+constexpr int SEG_WAVES = 4;  // rays (waves) per 256-thread block
+
+__device__ __forceinline__ float seg_dist(const SegCompArgs& a, int64_t r) {
+  const float* ray = a.rays + r * 6;
+  const float dx = ray[3], dy = ray[4], dz = ray[5];
+  return fmul(a.step_size, sqrtf(fadd(fadd(fmul(dx, dx), fmul(dy, dy)), fmul(dz, dz))));  // = the march's
+}
+
+// alpha of the point at k (lane-private); 0 for a lane past the segment or a surplus point
+__device__ __forceinline__ float seg_alpha(const SegCompArgs& a, int64_t k, int64_t end, float dist, int* step) {
+  *step = k < end ? a.out_step[k] : -1;
+  if (*step < 0) return 0.f;
+  const float s = a.raw[k * 4 + 3];
+  const float sigma = s > 0.f ? s : 0.f;
+  return fsub(1.f, expf(-fmul(sigma, dist)));
+}
+
+__device__ __forceinline__ double wave_prod_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v *= __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// prod (1 - alpha) over the 64 points from b (a chunk's transmittance factor; wave-uniform)
+__device__ __forceinline__ double seg_chunk_prod(const SegCompArgs& a, int64_t b, int64_t end, float dist) {
+  int st;
+  const float alpha = seg_alpha(a, b + lane_id(), end, dist, &st);
+  return wave_prod_d((double)fsub(1.f, alpha));
+}
+
+__device__ __forceinline__ float seg_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
+// One wave per ray, lanes on consecutive points (raw read as coalesced float4), 64 points a chunk:
+// T_k = T_in * prod_{j<k in chunk} (1 - alpha_j) by a product scan across the lanes (in double, as
+// the compositor of render()), T_in carried from chunk to chunk; every point of the segment is used.
+__global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompArgs a) {
+  const int64_t r = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+  if (r >= a.N) return;  // (wave-uniform)
+  const int l = lane_id();
+  const int64_t beg = a.seg_off[r], end = a.seg_off[r + 1];
+  const float dist = seg_dist(a, r);
+  double Tin = 1.0, sr = 0.0, sg = 0.0, sb = 0.0, sd = 0.0, sa = 0.0;
+  for (int64_t b = beg; b < end; b += 64) {
+    const int64_t k = b + l;
+    int st;
+    const float alpha = seg_alpha(a, k, end, dist, &st);
+    const double P = wave_scan_mul((double)fsub(1.f, alpha));
+    double Pex = __shfl_up(P, 1, 64);
+    if (l == 0) Pex = 1.0;
+    if (st >= 0) {
+      const float4 rw = *(const float4*)(a.raw + k * 4);
+      const double w = Tin * Pex * (double)alpha;
+      sr += w * (double)seg_sigmoid(rw.x);
+      sg += w * (double)seg_sigmoid(rw.y);
+      sb += w * (double)seg_sigmoid(rw.z);
+      sd += w * (double)a.t_table[st];
+      sa += w;
+    }
+    Tin *= shfl_d(P, 63);
+  }
+  sr = wave_sum_d(sr);
+  sg = wave_sum_d(sg);
+  sb = wave_sum_d(sb);
+  sd = wave_sum_d(sd);
+  sa = wave_sum_d(sa);
+  if (l == 0) {
+    const float acc = (float)sa;
+    const float bg = a.white ? fsub(1.f, acc) : 0.f;  // rgb += (1 - acc) * 1
+    a.rgb[r * 3 + 0] = fadd((float)sr, bg);
+    a.rgb[r * 3 + 1] = fadd((float)sg, bg);
+    a.rgb[r * 3 + 2] = fadd((float)sb, bg);
+    a.depth[r] = (float)sd;
+    a.acc[r] = acc;
+  }
+}
+
+// Backward, division-free.  With v_k = g_rgb . c_k + g_depth t_k + g_acc' (g_acc' = g_acc - sum g_rgb
+// on a white background) and R_k = sum_{j>k} w_j v_j / T_{k+1}, obtained without the division from
+// R_last = 0, R_{k-1} = alpha_k v_k + (1 - alpha_k) R_k:  dL/dalpha_k = T_k (v_k - R_k), dL/dc_k = w_k g_rgb.
+// R is a suffix composition of the affine maps x -> alpha_k v_k + (1 - alpha_k) x: a scan across the
+// lanes per chunk, the chunks walked in reverse with R carried.  The chunks' entry transmittances
+// come from a forward pre-pass and live in registers: lane j holds chunk j's (the first 64 chunks,
+// 4096 points: every ray of an 800-step march) and super-chunk j's (64 chunks each); a later
+// super-chunk's chunk entries are recomputed from its own entry when the reverse walk reaches it.
+// alpha_k = 1 (exp underflow) zeroes T from k + 1 on: every later gradient is exactly 0, no 0/0.
+__global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_bwd_kernel(SegCompArgs a) {
+  const int64_t r = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+  if (r >= a.N) return;  // (wave-uniform)
+  const int l = lane_id();
+  const int64_t beg = a.seg_off[r], end = a.seg_off[r + 1];
+  if (end <= beg) return;
+  const float dist = seg_dist(a, r);
+  const double gr = a.g_rgb ? (double)a.g_rgb[r * 3 + 0] : 0.0, gg = a.g_rgb ? (double)a.g_rgb[r * 3 + 1] : 0.0,
+               gb = a.g_rgb ? (double)a.g_rgb[r * 3 + 2] : 0.0;
+  const double gd = a.g_depth ? (double)a.g_depth[r] : 0.0;
+  const double ga = (a.g_acc ? (double)a.g_acc[r] : 0.0) - (a.white ? gr + gg + gb : 0.0);
+  const int64_t nchunks = (end - beg + 63) / 64, nsuper = (nchunks + 63) / 64;
+  double chunkT = 1.0, superT = 1.0;
+  {
+    double T = 1.0;
+    for (int64_t c = 0; c < nchunks; ++c) {
+      if (c < 64 && l == (int)c) chunkT = T;
+      if ((c & 63) == 0 && (c >> 6) < 64 && l == (int)(c >> 6)) superT = T;
+      if (c + 1 < nchunks) T *= seg_chunk_prod(a, beg + c * 64, end, dist);
+    }
+  }
+  double C = 0.0;  // R at the last point of the chunk in hand
+  for (int64_t sc = nsuper - 1; sc >= 0; --sc) {
+    const int64_t c0 = sc * 64, c1 = c0 + 64 < nchunks ? c0 + 64 : nchunks;
+    double cT = chunkT;  // lane j: T entering chunk c0 + j
+    if (sc > 0) {
+      double T = 1.0;
+      if (sc < 64) {
+        T = shfl_d(superT, (int)sc);
+      } else {
+        for (int64_t c = 0; c < c0; ++c) T *= seg_chunk_prod(a, beg + c * 64, end, dist);
+      }
+      for (int64_t c = c0; c < c1; ++c) {
+        if (l == (int)(c - c0)) cT = T;
+        if (c + 1 < c1) T *= seg_chunk_prod(a, beg + c * 64, end, dist);
+      }
+    }
+    for (int64_t c = c1 - 1; c >= c0; --c) {
+      const double Tin = shfl_d(cT, (int)(c - c0));
+      const int64_t k = beg + c * 64 + l;
+      int st;
+      const float alpha = seg_alpha(a, k, end, dist, &st);
+      const float om = fsub(1.f, alpha);
+      const double P = wave_scan_mul((double)om);
+      double Pex = __shfl_up(P, 1, 64);
+      if (l == 0) Pex = 1.0;
+      float4 rw = make_float4(0.f, 0.f, 0.f, 0.f);
+      float cx = 0.f, cy = 0.f, cz = 0.f;
+      double v = 0.0;
+      if (st >= 0) {
+        rw = *(const float4*)(a.raw + k * 4);
+        cx = seg_sigmoid(rw.x);
+        cy = seg_sigmoid(rw.y);
+        cz = seg_sigmoid(rw.z);
+        v = gr * (double)cx + gg * (double)cy + gb * (double)cz + gd * (double)a.t_table[st] + ga;
+      }
+      // suffix composition: (A, B) of lane i = f_i o f_{i+1} o ... o f_63, f_j(x) = alpha_j v_j + (1 - alpha_j) x
+      double A = (double)alpha * v, B = (double)om;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const double An = __shfl_down(A, o, 64), Bn = __shfl_down(B, o, 64);
+        if (l + o < 64) {
+          A += B * An;
+          B *= Bn;
+        }
+      }
+      const double An = __shfl_down(A, 1, 64), Bn = __shfl_down(B, 1, 64);
+      const double R = l == 63 ? C : An + Bn * C;
+      C = shfl_d(A, 0) + shfl_d(B, 0) * C;
+      if (k < end) {
+        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (st >= 0) {
+          const double T = Tin * Pex, w = T * (double)alpha;
+          const double dalpha = T * (v - R);
+          g.x = (float)(w * gr * (double)(cx * (1.f - cx)));
+          g.y = (float)(w * gg * (double)(cy * (1.f - cy)));
+          g.z = (float)(w * gb * (double)(cz * (1.f - cz)));
+          g.w = rw.w > 0.f ? (float)(dalpha * (double)dist * (double)om) : 0.f;
+        }
+        *(float4*)(a.g_raw + k * 4) = g;
+      }
+    }
+  }
 }
 
 }  // namespace nerf
@@ -685,15 +920,68 @@ int nerf_march_gather(const float* rays, int64_t N, const float* t_table, int n_
   return check_launch("nerf_march_emit");
 }
 
+int nerf_march_composite_used(const float* raw, const float* rays, int64_t N, const float* t_table,
+                              const int32_t* ray_off, const int32_t* ray_cnt, const int32_t* out_step, float* T,
+                              float* rgb, float* depth, float* acc, int32_t* next_step, uint8_t* alive,
+                              uint8_t* exhausted, float step_size, float t_thresh, unsigned long long* consumed,
+                              int32_t* ray_used, hipStream_t stream) {
+  if (N == 0) return 0;
+  MarchCompArgs a{raw, rays, N, t_table, ray_off, ray_cnt, out_step,
+                  {T, rgb, depth, acc, next_step, alive, exhausted}, step_size, t_thresh, consumed, ray_used};
+  hipLaunchKernelGGL(march_composite_kernel, grid1(N), dim3(256), 0, stream, a);
+  return check_launch("nerf_march_composite");
+}
+
 int nerf_march_composite(const float* raw, const float* rays, int64_t N, const float* t_table, const int32_t* ray_off,
                          const int32_t* ray_cnt, const int32_t* out_step, float* T, float* rgb, float* depth,
                          float* acc, int32_t* next_step, uint8_t* alive, uint8_t* exhausted, float step_size,
                          float t_thresh, unsigned long long* consumed, hipStream_t stream) {
+  return nerf_march_composite_used(raw, rays, N, t_table, ray_off, ray_cnt, out_step, T, rgb, depth, acc, next_step,
+                                   alive, exhausted, step_size, t_thresh, consumed, nullptr, stream);
+}
+
+int nerf_march_segments(const float* rays, int64_t N, const float* t_table, int n_steps, const uint8_t* grid, int res,
+                        const uint8_t* macro, const float* bbox_host, const int32_t* seg_off, int32_t* out_ray,
+                        int32_t* out_step, float* out_pts, hipStream_t stream) {
+  NERF_REQUIRE(N >= 0 && n_steps >= 0 && res > 1 && bbox_host, "nerf_march_segments: bad arguments");
+  NERF_REQUIRE(n_steps < 65536, "nerf_march_segments: needs n_steps < 65536 (the one-pass march's step range)");
+  NERF_REQUIRE(seg_off, "nerf_march_segments: seg_off is null");
   if (N == 0) return 0;
-  MarchCompArgs a{raw, rays, N, t_table, ray_off, ray_cnt, out_step,
-                  {T, rgb, depth, acc, next_step, alive, exhausted}, step_size, t_thresh, consumed};
-  hipLaunchKernelGGL(march_composite_kernel, grid1(N), dim3(256), 0, stream, a);
-  return check_launch("nerf_march_composite");
+  NERF_REQUIRE(rays && grid && (t_table || n_steps == 0), "nerf_march_segments: null pointer");
+  MarchGatherArgs a{rays, N, t_table, n_steps, grid, res, macro, make_bbox(bbox_host), 0, 0, 0.f,
+                    {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+                    nullptr, nullptr, out_ray, out_step, out_pts, nullptr, nullptr, 0};
+  hipLaunchKernelGGL(march_segments_kernel, grid1(N), dim3(256), 0, stream, a, seg_off);
+  return check_launch("nerf_march_segments");
+}
+
+static inline dim3 seg_grid(int64_t N) { return dim3((unsigned)((N + SEG_WAVES - 1) / SEG_WAVES)); }
+
+int nerf_march_seg_composite_fwd(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                 const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                 float* rgb, float* depth, float* acc, hipStream_t stream) {
+  NERF_REQUIRE(N >= 0, "nerf_march_seg_composite_fwd: N must be >= 0");
+  NERF_REQUIRE(seg_off, "nerf_march_seg_composite_fwd: seg_off is null");
+  if (N == 0) return 0;
+  NERF_REQUIRE(rays && rgb && depth && acc, "nerf_march_seg_composite_fwd: null pointer");
+  SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white, rgb, depth, acc,
+                nullptr, nullptr, nullptr, nullptr};
+  hipLaunchKernelGGL(march_seg_fwd_kernel, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  return check_launch("nerf_march_seg_composite_fwd");
+}
+
+int nerf_march_seg_composite_bwd(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                 const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                 const float* g_rgb, const float* g_depth, const float* g_acc, float* g_raw,
+                                 hipStream_t stream) {
+  NERF_REQUIRE(N >= 0, "nerf_march_seg_composite_bwd: N must be >= 0");
+  NERF_REQUIRE(seg_off, "nerf_march_seg_composite_bwd: seg_off is null");
+  if (N == 0) return 0;
+  NERF_REQUIRE(rays, "nerf_march_seg_composite_bwd: null pointer");
+  SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white, nullptr, nullptr, nullptr,
+                g_rgb, g_depth, g_acc, g_raw};
+  hipLaunchKernelGGL(march_seg_bwd_kernel, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  return check_launch("nerf_march_seg_composite_bwd");
 }
 
 int nerf_march_finish(float* rgb, const float* acc, int64_t N, int white, hipStream_t stream) {

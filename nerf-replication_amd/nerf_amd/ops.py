@@ -9,6 +9,7 @@ Reference interfaces mirrored (echo636/nerf-replication):
   mlp                  src/models/nerf/network.py:171-192 (autograd Function)
   grid_index           volume_renderer.py:261-265
   march                volume_renderer.py:268-357
+  march_grad           volume_renderer.py:268-357 called with autograd on (differentiable maps)
   bake                 occupancy_grid.py:15-80
   adam_step            src/train/trainers/trainer.py:61-62
 """
@@ -577,7 +578,7 @@ class _MLP(torch.autograd.Function):
             raise RuntimeError("the bf16x6 MLP is an inference forward only (no autograd, no density-only pass)")
         raw = torch.empty(M, 4, device=dev, dtype=torch.float32)
         if M == 0:
-            ctx.M = 0
+            ctx.M, ctx.packer = 0, packer  # (the backward returns zero gradients of the packer's parameters)
             return raw
         if viewdirs is not None:
             viewdirs = _f32c(viewdirs.reshape(-1, 3), "viewdirs")
@@ -760,7 +761,7 @@ def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: 
           t_thresh: float = 1e-4, bbox=SCENE_BBOX, white_bkgd: bool = True, dtype=F32,
           t_table: Optional[torch.Tensor] = None, k_schedule=(12, 24, 48, 96, 192, 384, 768),
           round_bytes: int = 1 << 31, k_low: int = 8, t_split: float = 0.9, sync_every: int = 4,
-          use_macro: bool = True, one_pass: bool = True, k_low_grow: int = 8):
+          use_macro: bool = True, one_pass: bool = True, k_low_grow: int = 8, return_used: bool = False):
     """Grid-accelerated march with early termination -> dict(rgb_map_f, depth_map_f,
     acc_map_f, n_queried, n_evaluated, rounds).
 
@@ -786,15 +787,28 @@ def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: 
     empty rounds after the last one).  The point buffer is sized once per call for the
     largest round the byte budget allows (up to round_bytes, ~2.1 GB at the default); it
     comes from PyTorch's caching allocator, so consecutive frames (and in-training
-    validation) reuse one block rather than allocating it again."""
+    validation) reuse one block rather than allocating it again.  With ``return_used`` the
+    result also carries ``ray_used`` (int32 [N]): the points composited per ray, summed over the
+    rounds (ray_used.sum() == n_queried); the other outputs are the same bit for bit."""
+    return _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table, k_schedule,
+                  round_bytes, k_low, t_split, sync_every, use_macro, one_pass, k_low_grow, return_used)[0]
+
+
+def _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table, k_schedule,
+           round_bytes, k_low, t_split, sync_every, use_macro, one_pass, k_low_grow, return_used):
+    """march() -> (its result, the walk's inputs for a second pass over the same rays: the
+    contiguous rays, the t table, the uint8 grid, its macro blocks, the unit view directions)."""
     rays = _f32c(rays.reshape(-1, 6), "rays")
     dev, N = rays.device, rays.shape[0]
     L = lib()
     s = stream_of(rays)
     if N == 0:
         z = torch.zeros(0, device=dev)
-        return {"rgb_map_f": torch.zeros(0, 3, device=dev), "depth_map_f": z, "acc_map_f": z.clone(), "n_queried": 0,
-                "n_evaluated": 0, "rounds": 0}
+        out = {"rgb_map_f": torch.zeros(0, 3, device=dev), "depth_map_f": z, "acc_map_f": z.clone(), "n_queried": 0,
+               "n_evaluated": 0, "rounds": 0}
+        if return_used:
+            out["ray_used"] = torch.zeros(0, dtype=torch.int32, device=dev)
+        return out, None
     if t_table is None:
         t_table = device_table("arange", float(near), float(far), float(step_size), dev)
     t_table = _f32c(t_table.to(dev), "t_table")
@@ -814,6 +828,7 @@ def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: 
     cnt = torch.empty(N, dtype=torch.int32, device=dev)
     counters = torch.zeros(2, dtype=torch.int32, device=dev)
     stats = torch.zeros(2, dtype=torch.int64, device=dev)  # [0] composited (queried), [1] evaluated
+    used = torch.zeros(N, dtype=torch.int32, device=dev) if return_used else None
     # the largest K times every ray, or the byte budget (a ray that does not fit waits a round)
     cap = max(1, min(N * max(k_schedule), round_bytes // MARCH_POINT_BYTES, 2 ** 31 - 1))
     cap = max(cap, max(k_schedule))
@@ -845,9 +860,10 @@ def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: 
                                   ptr(out_pts), ptr(off), ptr(cnt), cap, s), "nerf_march_gather")
         with torch.no_grad():
             mlp_count(packer, out_pts, vd, out_ray, counters, raw, dtype)
-        check(L.nerf_march_composite(ptr(raw), ptr(rays), N, ptr(t_table), ptr(off), ptr(cnt), ptr(out_step), ptr(T),
-                                     ptr(rgb), ptr(depth), ptr(acc), ptr(nxt), ptr(alive), ptr(exh),
-                                     float(step_size), float(t_thresh), stats.data_ptr(), s), "nerf_march_composite")
+        check(L.nerf_march_composite_used(ptr(raw), ptr(rays), N, ptr(t_table), ptr(off), ptr(cnt), ptr(out_step),
+                                          ptr(T), ptr(rgb), ptr(depth), ptr(acc), ptr(nxt), ptr(alive), ptr(exh),
+                                          float(step_size), float(t_thresh), stats.data_ptr(), ptr(used), s),
+              "nerf_march_composite")
         if rounds >= live_hist.numel():
             live_hist = torch.cat([live_hist, torch.zeros_like(live_hist)])
         live_hist[rounds:rounds + 1].copy_(counters[1:2])
@@ -857,8 +873,96 @@ def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: 
     check(L.nerf_march_finish(ptr(rgb), ptr(acc), N, int(bool(white_bkgd)), s), "nerf_march_finish")
     st = stats.tolist()
     live_rounds = int((live_hist[:rounds] > 0).sum())
-    return {"rgb_map_f": rgb, "depth_map_f": depth, "acc_map_f": acc, "n_queried": int(st[0]),
-            "n_evaluated": int(st[1]), "rounds": live_rounds, "rounds_launched": rounds}
+    out = {"rgb_map_f": rgb, "depth_map_f": depth, "acc_map_f": acc, "n_queried": int(st[0]),
+           "n_evaluated": int(st[1]), "rounds": live_rounds, "rounds_launched": rounds}
+    if return_used:
+        out["ray_used"] = used
+    return out, (rays, t_table, n_steps, g, res, macro, vd)
+
+
+class _MarchSegComposite(torch.autograd.Function):
+    """Compositing of per-ray segments of marched points (nerf_march_seg_composite_fwd / _bwd):
+    differentiable in raw, every point of a segment used (the march decided which, without grad)."""
+
+    @staticmethod
+    def forward(ctx, raw, rays, t_table, seg_off, out_step, step_size, white):
+        raw = _f32c(raw.reshape(-1, 4), "raw")
+        N, dev = rays.shape[0], rays.device
+        rgb = torch.empty(N, 3, device=dev, dtype=torch.float32)
+        depth = torch.empty(N, device=dev, dtype=torch.float32)
+        acc = torch.empty(N, device=dev, dtype=torch.float32)
+        M = raw.shape[0]
+        # bytes: raw 16 B + step 4 B per point; ray 24 B, offsets 4 B, rgb/depth/acc 20 B per ray
+        with kernel_timer("march_seg_composite_fwd", 20 * M + 48 * N, detail=True):
+            check(lib().nerf_march_seg_composite_fwd(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step),
+                                                     float(step_size), int(bool(white)), ptr(rgb), ptr(depth),
+                                                     ptr(acc), stream_of(rays)), "nerf_march_seg_composite_fwd")
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(raw, rays, t_table, seg_off, out_step)
+        ctx.step_size, ctx.white = float(step_size), int(bool(white))
+        return rgb, depth, acc
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_acc):
+        if g_rgb is None and g_depth is None and g_acc is None:
+            return (None,) * 7
+        raw, rays, t_table, seg_off, out_step = ctx.saved_tensors
+        N, M = rays.shape[0], raw.shape[0]
+        g = [None if t is None else _f32c(t, "cotangent") for t in (g_rgb, g_depth, g_acc)]
+        g_raw = torch.empty_like(raw)
+        # bytes: raw 16 B + step 4 B read twice (entry transmittances, then the reverse walk), d_raw 16 B written
+        with kernel_timer("march_seg_composite_bwd", 56 * M + 48 * N, detail=True):
+            check(lib().nerf_march_seg_composite_bwd(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step),
+                                                     ctx.step_size, ctx.white, ptr(g[0]), ptr(g[1]), ptr(g[2]),
+                                                     ptr(g_raw), stream_of(rays)), "nerf_march_seg_composite_bwd")
+        return (g_raw,) + (None,) * 6
+
+
+def march_segments(rays: torch.Tensor, t_table: torch.Tensor, grid_u8: torch.Tensor, macro: Optional[torch.Tensor],
+                   seg_off: torch.Tensor, M: int, bbox=SCENE_BBOX):
+    """Every ray's first seg_off[r+1] - seg_off[r] occupied steps, contiguous in ray order
+    (nerf_march_segments) -> out_ray [M] int32, out_step [M] int32 (-1: surplus), out_pts [M,3]."""
+    dev, N = rays.device, rays.shape[0]
+    out_ray = torch.empty(M, dtype=torch.int32, device=dev)
+    out_step = torch.empty(M, dtype=torch.int32, device=dev)
+    out_pts = torch.empty(M, 3, device=dev)
+    if M > 0:
+        check(lib().nerf_march_segments(ptr(rays), N, ptr(t_table), t_table.numel(), ptr(grid_u8),
+                                        int(grid_u8.shape[0]), ptr(macro), _bbox_arr(bbox), ptr(seg_off), ptr(out_ray),
+                                        ptr(out_step), ptr(out_pts), stream_of(rays)), "nerf_march_segments")
+    return out_ray, out_step, out_pts
+
+
+def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: torch.Tensor,
+               step_size: float = 0.005, t_thresh: float = 1e-4, bbox=SCENE_BBOX, white_bkgd: bool = True, dtype=F32,
+               t_table: Optional[torch.Tensor] = None, k_schedule=(12, 24, 48, 96, 192, 384, 768),
+               round_bytes: int = 1 << 31, use_macro: bool = True):
+    """march() whose maps carry an autograd graph back to the packer's parameters: what the
+    reference's render_accelerated gives when it is called with autograd on.  Two passes, in the
+    spirit of the detached sample_pdf of render().  Pass A is march() itself, without gradient:
+    it decides which points each ray composites (early termination and the speculative points
+    are handled there and nowhere else) and returns their per-ray counts.  Pass B lays those
+    points out contiguously in ray order (an exclusive prefix sum of the counts, no atomic
+    reservation: the sample order, and with it the dW sum order and the gradient, is the same
+    run to run), runs the training MLP on them once, and composites every segment with a
+    differentiable kernel pair.  M = n_queried comes from pass A's one host read; no other
+    host synchronisation.  Same keys as march(); M == 0 gives the background and zero gradients."""
+    with torch.no_grad():
+        out, walk = _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table,
+                           k_schedule, round_bytes, 8, 0.9, 4, use_macro, True, 8, True)
+    used = out.pop("ray_used")
+    if walk is None:  # no rays
+        return out
+    rays_c, t_tab, _, g8, _, macro, vd = walk
+    N, M = rays_c.shape[0], out["n_queried"]
+    seg_off = torch.zeros(N + 1, dtype=torch.int32, device=rays_c.device)
+    seg_off[1:] = torch.cumsum(used, 0, dtype=torch.int32)
+    out_ray, out_step, out_pts = march_segments(rays_c, t_tab, g8, macro, seg_off, M, bbox)
+    raw = mlp(packer, out_pts, vd, 1, out_ray, dtype)
+    rgb, depth, acc = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size),
+                                               bool(white_bkgd))
+    out.update(rgb_map_f=rgb, depth_map_f=depth, acc_map_f=acc)
+    return out
 
 
 # --------------------------------------------------------------------------------------

@@ -32,6 +32,12 @@ FRAGILE_ABS_TOL = 1.2e-7
 FRAGILE_DEN_TOL = 0.0
 FRAGILE_Z_TOL = 0.0
 
+# points gathered per ray and round by the no-grad pass of the differentiable march (task_arg.train_k_schedule).  A
+# training chunk is a few thousand rays, where the march's rounds are launch-bound: 4 rounds instead of the inference
+# schedule's 12 made the whole 4096-ray step 1.2-1.5x faster, although the inference MLP then evaluates 1.8x the points
+# (tools/march_train_bench.py, profiles/r7/march_train.json).  The schedule changes no output
+TRAIN_K_SCHEDULE = (96, 384, 768)
+
 
 class Renderer:
     def __init__(self, net):
@@ -183,8 +189,35 @@ class Renderer:
         idx, _ = ops.grid_index(points, None, int(self.grid_resolution[0]), self._bbox_tuple())
         return idx
 
+    def _render_accelerated_grad(self, rays_flat, near, far):
+        """render_accelerated under autograd (ops.march_grad): the maps carry a graph back to the fine
+        net, as the reference's plain-torch march does.  Rays in chunks of task_arg.chunk_size,
+        concatenated, as render() does; no device-wide synchronisation (render_time is host time)."""
+        ta = cfg.task_arg
+        start = time.time()
+        chunk = self._chunk(True)
+        packer = self.net.model_fine.packer()
+        sched = tuple(int(k) for k in ta.get("train_k_schedule", TRAIN_K_SCHEDULE))
+        maps = {"rgb_map_f": [], "depth_map_f": [], "acc_map_f": []}
+        counts = {"n_queried": 0, "n_evaluated": 0, "rounds": 0}
+        for i in range(0, rays_flat.shape[0], chunk):
+            out = ops.march_grad(packer, rays_flat[i:i + chunk], near, far, self.occupancy_grid,
+                                 step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
+                                 bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
+                                 k_schedule=sched)
+            for k, v in maps.items():
+                v.append(out[k])
+            for k in counts:
+                counts[k] += out[k]
+        ret = {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in maps.items()}
+        ret["render_time"] = time.time() - start
+        ret.update(counts)
+        return ret
+
     def render_accelerated(self, batch):
-        """volume_renderer.py:268-357: march the fine net through the occupancy grid."""
+        """volume_renderer.py:268-357: march the fine net through the occupancy grid.  With autograd on
+        and a fine-net parameter requiring grad the maps are differentiable (_render_accelerated_grad);
+        otherwise (every inference caller runs under no_grad) the march alone."""
         if self.occupancy_grid is None:
             print("Occupancy grid not loaded, running in slow mode.")
             return self.render(batch)
@@ -193,6 +226,8 @@ class Renderer:
         rays_flat = rays.reshape(-1, 6) if rays.ndim == 3 else rays
         near = float(batch["near"].reshape(-1)[0]) if torch.is_tensor(batch["near"]) else float(batch["near"])
         far = float(batch["far"].reshape(-1)[0]) if torch.is_tensor(batch["far"]) else float(batch["far"])
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.net.model_fine.parameters()):
+            return self._render_accelerated_grad(rays_flat, near, far)
         starter = torch.cuda.Event(enable_timing=True)
         ender = torch.cuda.Event(enable_timing=True)
         starter.record()
