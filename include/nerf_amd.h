@@ -265,6 +265,33 @@ int nerf_march_seg_composite_bwd(const float* raw, const float* rays, int64_t N,
                                  const float* g_rgb, const float* g_depth, const float* g_acc, float* g_raw,
                                  hipStream_t stream);
 
+/* ---- (a13) online occupancy grid: the trainer maintains the grid from the live fine net -----------
+ * State: a fp32 density[res^3] in the march's (ix*res + iy)*res + iz order and the uint8 grid the
+ * march reads.  No allocation, no host synchronisation; 2 <= res <= 1290 (cell ids are int32).
+ *
+ * nerf_grid_update_points: for the n slots [s0, s0 + n) of the bijection pi(s) = (s * stride_a +
+ * offset_b) mod res^3 (stride_a in (0, res^3) and coprime to res^3, else an error: a cell appears at
+ * most once per update) writes cells[n] = pi(s) and pts[n,3] = one jittered point inside that cell --
+ * the cell of nerf_grid_index: index i < res - 1 covers the normalised coordinate [i / (res-1),
+ * (i+1) / (res-1)), index res - 1 is sampled at the bbox face.  Every coordinate is checked against
+ * the lookup and replaced by the cell's centre when fp32 rounding put it in a neighbour.  The jitter
+ * is Philox keyed by seed and counted by (update, slot): the same on every rank.
+ *
+ * nerf_grid_update_apply: density[cells[i]] = max(density[cells[i]] * decay, relu(raw[i,3])) for
+ * raw [n,4] (the density-only MLP's output on pts); other cells are untouched.
+ *
+ * nerf_grid_update_threshold: mean of density by a fixed-order two-level sum in the workspace
+ * (nerf_grid_update_workspace_bytes(res); no float atomics: bitwise reproducible), then grid[c] =
+ * density[c] > min(threshold, mean).  stats (device, 16 bytes): float mean, float min(threshold,
+ * mean), int32 occupied cells, int32 0. */
+int nerf_grid_update_points(int res, const float* bbox_host, uint64_t stride_a, uint64_t offset_b, uint64_t seed,
+                            uint64_t update, int64_t s0, int64_t n, int32_t* cells, float* pts, hipStream_t stream);
+int nerf_grid_update_apply(const int32_t* cells, const float* raw, int64_t n, int res, float decay, float* density,
+                           hipStream_t stream);
+int64_t nerf_grid_update_workspace_bytes(int res);
+int nerf_grid_update_threshold(const float* density, int res, float threshold, void* workspace, uint8_t* grid,
+                               void* stats, hipStream_t stream);
+
 /* ---- (a10) clip_grad_value_ + Adam (src/train/trainers/trainer.py:61-62, optimizer.py:8-28) ---- */
 int nerf_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
                    double beta2, double eps, int64_t step, double clip_value, hipStream_t stream);

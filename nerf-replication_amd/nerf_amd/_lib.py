@@ -73,6 +73,10 @@ SIGNATURES = {
     "nerf_march_segments": (_i32, [_p, _i64, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "nerf_march_seg_composite_fwd": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p]),
     "nerf_march_seg_composite_bwd": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _p]),
+    "nerf_grid_update_points": (_i32, [_i32, _p, _u64, _u64, _u64, _u64, _i64, _i64, _p, _p, _p]),
+    "nerf_grid_update_apply": (_i32, [_p, _p, _i64, _i32, _f32, _p, _p]),
+    "nerf_grid_update_workspace_bytes": (_i64, [_i32]),
+    "nerf_grid_update_threshold": (_i32, [_p, _i32, _f32, _p, _p, _p, _p]),
     "nerf_metrics_workspace_bytes": (_i64, [_i32, _i32]),
     "nerf_image_metrics": (_i32, [_p, _p, _i32, _i32, _p, _p, _p]),
     "nerf_adam_step": (_i32, [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _p]),

@@ -743,6 +743,95 @@ def bake(packer: PackedMLP, res: int, threshold: float, bbox=SCENE_BBOX, dtype=F
     return grid.bool()
 
 
+# --------------------------------------------------------------------------------------
+# online grid update (the trainer's grid, maintained from the live fine net)
+# --------------------------------------------------------------------------------------
+def grid_update_stride(res: int) -> int:
+    """The stride A of the slot -> cell bijection pi(s) = (s A + B) mod res^3: the integer nearest
+    0.618 res^3 (consecutive slots land far apart) or the next one above it coprime to res^3."""
+    import math
+    C = int(res) ** 3
+    if res < 2:
+        raise ValueError(f"grid_update_stride: res must be >= 2, got {res}")
+    a = max(1, min(C - 1, int(round(0.6180339887498949 * C))))
+    while math.gcd(a, C) != 1:
+        a += 1  # (C - 1 is coprime to C, so the walk ends below C)
+    return a
+
+
+def grid_update_slots(update: int, res: int, warmup_updates: int, period: int):
+    """(s0, n): the slots update ``update`` visits -- every cell during the warm-up, afterwards the
+    (update mod period)-th of ``period`` ranges of ceil(res^3 / period) slots, clipped to res^3."""
+    C = int(res) ** 3
+    if update < warmup_updates:
+        return 0, C
+    per = -(-C // int(period))
+    s0 = (update % int(period)) * per
+    return s0, max(0, min(per, C - s0))
+
+
+def grid_update_points(res: int, bbox, s0: int, n: int, update: int, seed: int = 0, device=None,
+                       stride: Optional[int] = None, offset: int = 0):
+    """-> cells [n] int32 (pi(s0 .. s0 + n)), pts [n,3]: one jittered point inside each cell
+    (nerf_grid_update_points)."""
+    device = torch.device(device if device is not None else "cuda")
+    if device.type != "cuda":
+        raise RuntimeError("nerf_amd kernels run on the GPU only (got a CPU device); there is no CPU fallback")
+    cells = torch.empty(int(n), dtype=torch.int32, device=device)
+    pts = torch.empty(int(n), 3, dtype=torch.float32, device=device)
+    a = grid_update_stride(res) if stride is None else int(stride)
+    check(lib().nerf_grid_update_points(int(res), _bbox_arr(bbox), a, int(offset), int(seed), int(update), int(s0),
+                                        int(n), ptr(cells), ptr(pts), stream_of(pts)), "nerf_grid_update_points")
+    return cells, pts
+
+
+def grid_update_apply(density: torch.Tensor, cells: torch.Tensor, raw: torch.Tensor, decay: float) -> torch.Tensor:
+    """density[cells[i]] = max(density[cells[i]] * decay, relu(raw[i,3])), in place (density: fp32
+    [res,res,res] or [res^3]; nerf_grid_update_apply)."""
+    if density.dtype != torch.float32 or not density.is_contiguous():
+        raise TypeError("grid_update_apply: density must be a contiguous float32 tensor")
+    if cells.dtype != torch.int32 or not cells.is_contiguous():
+        raise TypeError("grid_update_apply: cells must be a contiguous int32 tensor")
+    raw = _f32c(raw.reshape(-1, 4), "raw")
+    n = cells.numel()
+    if raw.shape[0] != n:
+        raise ValueError(f"grid_update_apply: {n} cells but {raw.shape[0]} rows of raw")
+    res = round(density.numel() ** (1.0 / 3.0))
+    if res ** 3 != density.numel():
+        raise ValueError("grid_update_apply: density must hold res^3 values")
+    check(lib().nerf_grid_update_apply(ptr(cells), ptr(raw), n, res, float(decay), ptr(density), stream_of(density)),
+          "nerf_grid_update_apply")
+    return density
+
+
+def grid_update_threshold(density: torch.Tensor, grid: torch.Tensor, threshold: float,
+                          workspace: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None):
+    """grid[c] = density[c] > min(threshold, mean(density)), in place (grid: uint8, density's shape);
+    -> stats, an int32 [4] device tensor: [0] the mean and [1] the cut as float32 bits, [2] the occupied
+    count (grid_update_stats reads it; nerf_grid_update_threshold)."""
+    if density.dtype != torch.float32 or not density.is_contiguous():
+        raise TypeError("grid_update_threshold: density must be a contiguous float32 tensor")
+    if grid.dtype != torch.uint8 or not grid.is_contiguous() or grid.numel() != density.numel():
+        raise TypeError("grid_update_threshold: grid must be a contiguous uint8 tensor of the density's size")
+    res = round(density.numel() ** (1.0 / 3.0))
+    if res ** 3 != density.numel():
+        raise ValueError("grid_update_threshold: density must hold res^3 values")
+    dev = density.device
+    if workspace is None:
+        workspace = torch.empty(lib().nerf_grid_update_workspace_bytes(res), dtype=torch.uint8, device=dev)
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.int32, device=dev)
+    check(lib().nerf_grid_update_threshold(ptr(density), res, float(threshold), ptr(workspace), ptr(grid), ptr(stats),
+                                           stream_of(density)), "nerf_grid_update_threshold")
+    return stats
+
+
+def grid_update_stats(stats: torch.Tensor):
+    """(mean, occupied cells) of a grid_update_threshold stats buffer (a host read: synchronises)."""
+    s = stats.cpu()
+    return float(s[:1].view(torch.float32)[0]), int(s[2])
+
+
 MARCH_POINT_BYTES = 4 + 4 + 12 + 16  # out_ray, out_step, out_pts, raw per gathered point
 
 

@@ -180,6 +180,20 @@ class Renderer:
         self.scene_bbox = torch.tensor(cfg.train_dataset.scene_bbox, device=device, dtype=torch.float32)
         self.voxel_size = (self.scene_bbox[1] - self.scene_bbox[0]) / self.grid_resolution
 
+    def set_live_grid(self, grid_u8):
+        """The trainer's own grid (OnlineGrid.grid: uint8 [res,res,res] on the device, rewritten in place
+        by its updates), taken as it is -- the march reads uint8, so no conversion per step."""
+        if grid_u8.dtype != torch.uint8 or grid_u8.dim() != 3 or not grid_u8.is_contiguous():
+            raise ValueError("the live occupancy grid must be a contiguous 3-D uint8 tensor")
+        if self.occupancy_grid is grid_u8:
+            return
+        device = grid_u8.device
+        self.occupancy_grid = grid_u8
+        self.grid_resolution = torch.tensor(grid_u8.shape, device=device)
+        self.resolution = int(grid_u8.shape[0])
+        self.scene_bbox = torch.tensor(cfg.train_dataset.scene_bbox, device=device, dtype=torch.float32)
+        self.voxel_size = (self.scene_bbox[1] - self.scene_bbox[0]) / self.grid_resolution
+
     def _bbox_tuple(self):
         b = cfg.train_dataset.scene_bbox
         return (tuple(float(v) for v in b[0]), tuple(float(v) for v in b[1]))

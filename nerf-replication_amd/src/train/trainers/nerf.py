@@ -11,6 +11,14 @@ loss = MSE(rgb_map_f, gt), stats {loss_f, total_loss}; the coarse net is not eva
 receives a zero gradient.  The grid comes from logs/<cfg name>/occupancy_grid.pt (what
 occupancy_grid.py writes and run.py evaluate loads); a missing file is an error, never a
 fall-back to the hierarchical render.  Without grad (validation) forward() keeps render().
+
+``task_arg.train_grid: online`` (default ``file``: the above; only with ``train_renderer:
+accelerated``) needs no grid file: the module owns an OnlineGrid for the FINE net (the net the
+march queries; the coarse net is not trained in this mode), updated from the live weights every
+``task_arg.grid_update.interval`` steps, so a run can start from random weights.  Validation
+(no grad) then also goes through render_accelerated with the live grid -- an untrained coarse
+net would make render()'s importance sampling meaningless -- with stats {loss_f, total_loss}.
+save_grid() / load_grid() write and read the grid beside the checkpoints (train.py).
 """
 import os
 
@@ -20,9 +28,12 @@ import torch.nn as nn
 from nerf_amd import ops
 
 from src.config import cfg
+from src.models.nerf.renderer.online_grid import OnlineGrid, grid_update_settings
 from src.models.nerf.renderer.volume_renderer import Renderer
 
 TRAIN_RENDERERS = ("hierarchical", "accelerated")
+TRAIN_GRIDS = ("file", "online")
+GRID_STATE_FILE = "occupancy_grid_state.pt"
 
 
 def occupancy_grid_path():
@@ -41,7 +52,19 @@ class NetworkWrapper(nn.Module):
         self.train_renderer = str(cfg.task_arg.get("train_renderer", "hierarchical") or "hierarchical")
         if self.train_renderer not in TRAIN_RENDERERS:
             raise ValueError(f"task_arg.train_renderer must be one of {TRAIN_RENDERERS}, got {self.train_renderer!r}")
-        if self.train_renderer == "accelerated":
+        self.train_grid = str(cfg.task_arg.get("train_grid", "file") or "file")
+        if self.train_grid not in TRAIN_GRIDS:
+            raise ValueError(f"task_arg.train_grid must be one of {TRAIN_GRIDS}, got {self.train_grid!r}")
+        self.online_grid = None
+        if self.train_grid == "online":
+            if self.train_renderer != "accelerated":
+                raise ValueError("task_arg.train_grid: online maintains the grid of train_renderer: accelerated; "
+                                 f"with train_renderer: {self.train_renderer} there is no grid to maintain")
+            ta = cfg.task_arg
+            self.online_grid = OnlineGrid(int(ta.get("occupancy_grid_res", 128)),
+                                          float(ta.get("occupancy_grid_threshold", 1.0)),
+                                          cfg.train_dataset.scene_bbox, **grid_update_settings(ta))
+        elif self.train_renderer == "accelerated":
             path = occupancy_grid_path()
             if not os.path.exists(path):
                 raise FileNotFoundError(
@@ -49,8 +72,45 @@ class NetworkWrapper(nn.Module):
                     "occupancy_grid.py (there is no fall-back to the hierarchical render in training)")
             self.renderer.load_occupancy_grid(path)
 
+    def _live_grid(self, device):
+        """The online grid on the rays' device, installed in the renderer (its uint8 tensor itself)."""
+        grid = self.online_grid.to(device)
+        self.renderer.set_live_grid(grid.grid)
+        return grid
+
+    def save_grid(self, model_dir):
+        """Online mode, beside a checkpoint: logs/<cfg name>/occupancy_grid.pt in occupancy_grid.py's bool
+        format (run.py evaluate and render_video.py load it) and <model_dir>/occupancy_grid_state.pt
+        (density, counters, settings: what a resumed run continues from).  A no-op in file mode."""
+        if self.online_grid is None:
+            return
+        path = occupancy_grid_path()
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        torch.save(self.online_grid.occupancy_bool(), path)
+        os.makedirs(model_dir, exist_ok=True)
+        torch.save(self.online_grid.state_dict(), os.path.join(model_dir, GRID_STATE_FILE))
+
+    def load_grid(self, model_dir):
+        """Resume: the state save_grid wrote, when it is there.  True when it was loaded."""
+        path = os.path.join(model_dir, GRID_STATE_FILE)
+        if self.online_grid is None or not os.path.exists(path):
+            return False
+        self.online_grid.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+        print(f"load occupancy grid state: {path}")
+        return True
+
     def forward(self, batch):
         gt = batch["rgbs"].reshape(-1, 3) if batch["rgbs"].dim() == 3 else batch["rgbs"]
+        if self.online_grid is not None:
+            grid = self._live_grid(batch["rays"].device)
+            fine = self.net.model_fine
+            if torch.is_grad_enabled():
+                grid.step(fine.packer(), self.net.mlp_dtype)  # (may update; update 0 precedes the first march)
+            elif grid.updates == 0:  # validation before any training step: never march the all-ones grid
+                grid.update(fine.packer(), self.net.mlp_dtype)
+            ret = self.renderer.render_accelerated(batch)
+            loss_f, _, total = ops.mse_pair(ret["rgb_map_f"], None, gt)
+            return ret, total, {"loss_f": loss_f, "total_loss": total}
         if self.train_renderer == "accelerated" and torch.is_grad_enabled():
             # the fine net through the grid march; the MSE and its backward in one launch each
             # (ops.mse_pair with no second image)

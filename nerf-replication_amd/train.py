@@ -21,6 +21,11 @@ from src.config import cfg, args  # noqa: E402
 from src.config.config import apply_gpus  # noqa: E402
 
 
+def save_grid(loss_module, model_dir):
+    if hasattr(loss_module, "save_grid"):
+        loss_module.save_grid(model_dir)
+
+
 def train(cfg, network):
     from src.datasets import make_data_loader
     from src.evaluators import make_evaluator
@@ -37,6 +42,11 @@ def train(cfg, network):
     recorder = make_recorder(cfg)
     evaluator = make_evaluator(cfg)
     begin_epoch = load_model(network, optimizer, scheduler, recorder, cfg.trained_model_dir, resume=cfg.resume)
+    # task_arg.train_grid: online -- the trainer's occupancy grid travels beside the checkpoints (the loss
+    # module's save_grid / load_grid; both are no-ops in file mode)
+    loss_module = trainer.network
+    if begin_epoch > 0 and hasattr(loss_module, "load_grid"):
+        loss_module.load_grid(cfg.trained_model_dir)
     if begin_epoch == 0 and cfg.pretrain != "":
         load_pretrain(network, cfg.pretrain)
     set_lr_scheduler(cfg, scheduler)
@@ -46,8 +56,10 @@ def train(cfg, network):
         scheduler.step()
         if (epoch + 1) % cfg.save_ep == 0 and cfg.local_rank == 0:
             save_model(network, optimizer, scheduler, recorder, cfg.trained_model_dir, epoch)
+            save_grid(loss_module, cfg.trained_model_dir)
         if (epoch + 1) % cfg.save_latest_ep == 0 and cfg.local_rank == 0:
             save_model(network, optimizer, scheduler, recorder, cfg.trained_model_dir, epoch, last=True)
+            save_grid(loss_module, cfg.trained_model_dir)
         if (epoch + 1) % cfg.eval_ep == 0 and cfg.local_rank == 0:
             trainer.val(epoch, val_loader, evaluator, recorder)
     return network

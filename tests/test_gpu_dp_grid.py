@@ -1,0 +1,111 @@
+"""Data-parallel training with the online occupancy grid (task_arg.train_grid "online") on two ranks.
+
+Two processes share cuda:0 over gloo, as in test_gpu_dp.py.  Each rank draws its own rays of a
+synthetic scene and runs the production step through the grid march; every rank runs the same grid
+update redundantly (same seed, same points, and -- after the gradient all-reduce -- the same
+weights), with no collective of its own.  After 2 * interval + 1 steps (three updates: two full, one
+rolling) the densities, the occupancies and the weights are bit-equal across the ranks.
+"""
+import os
+import socket
+
+import numpy as np
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+INTERVAL = 4
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _worker(rank, world, port, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                      LOCAL_RANK=str(rank), NERF_AMD_NO_ARGV="1")
+    import sys
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "nerf-replication_amd")]
+    try:
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        torch.cuda.set_device(0)
+        from nerf_amd import ops
+        from src.config import cfg
+        from src.datasets.nerf.blender import Dataset
+        from src.datasets.nerf.synthetic import view_poses
+        from src.models.nerf.network import Network
+        from src.train.optimizer import make_optimizer
+        from src.train.trainers.make_trainer import make_trainer
+        from src.utils.camera import focal_for
+        dev = torch.device("cuda", 0)
+        ta = cfg.task_arg
+        ta.perturb = 0
+        ta.mlp_dtype = "fp32"
+        ta.train_rays = 1024
+        ta.train_renderer = "accelerated"
+        ta.train_grid = "online"
+        ta.occupancy_grid_res = 64
+        ta.grid_update = {"interval": INTERVAL, "warmup_updates": 2, "period": 4}
+        z = np.load(os.path.join(HERE, "golden", "trained_v2.npz"), allow_pickle=False)
+        torch.manual_seed(0)
+        net = Network()
+        net.load_state_dict({k: torch.from_numpy(z[k]) for k in z.files}, strict=True)
+        net = net.to(dev)
+        trainer = make_trainer(cfg, net)
+        opt = make_optimizer(cfg, net)
+        images = torch.rand(4, 128, 128, 3, generator=torch.Generator().manual_seed(7)).to(dev)
+        ds = Dataset.from_arrays(images, view_poses(4, seed=3).to(dev), focal_for(128))
+        first = None
+        for _ in range(2 * INTERVAL + 1):
+            rays, rgbs = ds.sample_batch()
+            if first is None:
+                first = rays.cpu()
+            trainer.train_step({"rays": rays[None], "rgbs": rgbs[None], "near": ops.device_scalar(2.0, dev),
+                                "far": ops.device_scalar(6.0, dev)}, opt)
+        torch.cuda.synchronize()
+        grid = trainer.network.online_grid
+        mine = {"rays": first, "density": grid.density.cpu(), "grid": grid.grid.cpu(), "params": opt.flat_param.cpu()}
+        same = {}
+        for k, t in mine.items():
+            every = [torch.empty_like(t) for _ in range(world)]
+            dist.all_gather(every, t)
+            same[k] = all(torch.equal(every[0], e) for e in every[1:])
+        occupied = float(grid.grid.float().mean())
+        q.put((rank, same, (grid.updates, grid.steps), occupied, float(grid.density.max()), None))
+        dist.destroy_process_group()
+    except Exception:  # noqa: BLE001 - reported to the parent
+        import traceback
+        q.put((rank, None, None, None, None, traceback.format_exc()))
+
+
+def test_two_ranks_hold_the_same_grid():
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    try:
+        res = [q.get(timeout=240) for _ in procs]
+    finally:
+        for p in procs:
+            p.join(timeout=60)
+            if p.is_alive():
+                p.kill()
+    assert sorted(r[0] for r in res) == [0, 1]
+    for rank, same, counters, occupied, dmax, err in res:
+        assert err is None, err
+        assert counters == (3, 2 * INTERVAL + 1)  # updates at the grid's steps 0, interval, 2 interval
+        assert not same["rays"]  # each rank drew its own rays
+        assert same["density"] and same["grid"] and same["params"], (rank, same)
+        assert 0.0 < occupied < 1.0 and dmax > 0.0
+    for p in procs:
+        assert p.exitcode == 0
