@@ -265,6 +265,18 @@ int nerf_march_seg_composite_bwd(const float* raw, const float* rays, int64_t N,
                                  const float* g_rgb, const float* g_depth, const float* g_acc, float* g_raw,
                                  hipStream_t stream);
 
+/* ---- (a12) point budget: pass A's counts -> pass B's segments, cut at a budget of points ---------------
+ * ray_used[N] (int32, >= 0) -> seg_off[N+1] (int32) and keep[2] (int64, device):
+ * P[r] = sum_{q<r} ray_used[q] in 64-bit;  n_keep = the largest r in [0, N] with P[r] <= budget;
+ * m_keep = P[n_keep];  seg_off[r] = P[r] for r <= n_keep, m_keep for r > n_keep (dropped rays own
+ * zero-length segments);  keep = {n_keep, m_keep}.  0 <= budget <= INT32_MAX, else -22.
+ * One launch of one workgroup (no workgroup waits on another), integer-only, so deterministic; totals
+ * above 2^31 are fine (64-bit sums; everything written is <= budget).  N = 0 writes seg_off[0] = 0 and
+ * keep = {0, 0}.  keep is a plain pointer so that it can alias spare slots of a buffer the caller reads
+ * back anyway (the march's int64 stats): the budget then costs no host synchronisation of its own. */
+int nerf_march_budget(const int32_t* ray_used, int64_t N, int64_t budget, int32_t* seg_off, int64_t* keep,
+                      hipStream_t stream);
+
 /* ---- (a13) online occupancy grid: the trainer maintains the grid from the live fine net -----------
  * State: a fp32 density[res^3] in the march's (ix*res + iy)*res + iz order and the uint8 grid the
  * march reads.  No allocation, no host synchronisation; 2 <= res <= 1290 (cell ids are int32).

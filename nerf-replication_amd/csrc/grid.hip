@@ -797,6 +797,77 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_bwd_kernel(SegCompAr
 }
 
 // ------------------------------------------------------------------------------------
+// point budget: pass A's per-ray counts -> pass B's segment offsets, cut at a point budget
+// ------------------------------------------------------------------------------------
+// P[r] = sum_{q<r} used[q] (64-bit), n_keep = the largest r with P[r] <= budget, m_keep = P[n_keep];
+// seg_off[r] = P[r] up to n_keep and m_keep after it, so the rays past the cut own empty segments.
+// One workgroup walks the array in tiles of its size and carries the prefix: lanes scan within a
+// wave, the wave totals go through LDS.  No workgroup waits on another (there is only one), the
+// loads and stores are coalesced, and at the ray counts of a training step the launch is all it
+// costs.  Every value stored is <= budget <= INT32_MAX.
+constexpr int BUDGET_THREADS = 1024;
+constexpr int BUDGET_WAVES = BUDGET_THREADS / WAVE;
+
+__device__ __forceinline__ long long wave_scan_add_i64(long long v) {
+  const int l = lane_id();
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long t = __shfl_up(v, o, 64);
+    if (l >= o) v += t;
+  }
+  return v;
+}
+
+__global__ void __launch_bounds__(BUDGET_THREADS) march_budget_kernel(const int32_t* __restrict__ used, int64_t N,
+                                                                      long long budget, int32_t* __restrict__ seg_off,
+                                                                      int64_t* __restrict__ keep) {
+  __shared__ long long wave_tot[BUDGET_WAVES];
+  __shared__ long long cut[2];  // {n_keep, m_keep}; n_keep < 0: every ray so far fits
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+  if (tid == 0) {
+    seg_off[0] = 0;
+    cut[0] = -1;
+    cut[1] = 0;
+  }
+  __syncthreads();
+  long long carry = 0;  // P[base] <= budget
+  int64_t base = 0;
+  bool found = false;
+  for (; base < N && !found; base += BUDGET_THREADS) {
+    const int64_t r = base + tid;
+    const long long v = r < N ? (long long)used[r] : 0;
+    const long long inc = wave_scan_add_i64(v);
+    if (lane == WAVE - 1) wave_tot[w] = inc;
+    __syncthreads();
+    long long pre = carry, tot = 0;
+#pragma unroll
+    for (int k = 0; k < BUDGET_WAVES; ++k) {
+      const long long t = wave_tot[k];
+      if (k < w) pre += t;
+      tot += t;
+    }
+    const long long hi = pre + inc, lo = hi - v;  // P[r+1], P[r]
+    // the counts are >= 0, so P is monotone and at most one ray straddles the budget: the first dropped one
+    if (r < N && hi > budget && lo <= budget) {
+      cut[0] = r;
+      cut[1] = lo;
+    }
+    __syncthreads();  // (also orders this tile's reads of wave_tot before the next tile's writes)
+    found = cut[0] >= 0;
+    if (r < N) seg_off[r + 1] = (int32_t)(hi <= budget ? hi : cut[1]);
+    carry += tot;
+  }
+  if (found) {  // the tiles after the cut: m_keep everywhere, the counts are not read
+    const int32_t m = (int32_t)cut[1];
+    for (int64_t r = base + tid; r < N; r += BUDGET_THREADS) seg_off[r + 1] = m;
+  }
+  if (tid == 0) {
+    keep[0] = found ? cut[0] : N;
+    keep[1] = found ? cut[1] : carry;
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // online grid update (training from scratch through the march)
 // ------------------------------------------------------------------------------------
 // The trainer keeps a fp32 density per cell and re-derives the uint8 occupancy the march reads.
@@ -1091,6 +1162,18 @@ int nerf_march_seg_composite_bwd(const float* raw, const float* rays, int64_t N,
                 g_rgb, g_depth, g_acc, g_raw};
   hipLaunchKernelGGL(march_seg_bwd_kernel, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
   return check_launch("nerf_march_seg_composite_bwd");
+}
+
+int nerf_march_budget(const int32_t* ray_used, int64_t N, int64_t budget, int32_t* seg_off, int64_t* keep,
+                      hipStream_t stream) {
+  NERF_REQUIRE(N >= 0, "nerf_march_budget: N must be >= 0");
+  NERF_REQUIRE(budget >= 0 && budget <= (int64_t)INT32_MAX,
+               "nerf_march_budget: budget must be in [0, INT32_MAX] (the offsets are int32), got %lld",
+               (long long)budget);
+  NERF_REQUIRE(seg_off && keep && (ray_used || N == 0), "nerf_march_budget: null pointer");
+  hipLaunchKernelGGL(march_budget_kernel, dim3(1), dim3(BUDGET_THREADS), 0, stream, ray_used, N, (long long)budget,
+                     seg_off, keep);
+  return check_launch("nerf_march_budget");
 }
 
 // ---- online grid update ----

@@ -10,6 +10,7 @@ Reference interfaces mirrored (echo636/nerf-replication):
   grid_index           volume_renderer.py:261-265
   march                volume_renderer.py:268-357
   march_grad           volume_renderer.py:268-357 called with autograd on (differentiable maps)
+  march_budget         (no counterpart) the segment layout of march_grad(max_points=) under a point cap
   bake                 occupancy_grid.py:15-80
   adam_step            src/train/trainers/trainer.py:61-62
 """
@@ -884,9 +885,12 @@ def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: 
 
 
 def _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table, k_schedule,
-           round_bytes, k_low, t_split, sync_every, use_macro, one_pass, k_low_grow, return_used):
+           round_bytes, k_low, t_split, sync_every, use_macro, one_pass, k_low_grow, return_used, budget=None):
     """march() -> (its result, the walk's inputs for a second pass over the same rays: the
-    contiguous rays, the t table, the uint8 grid, its macro blocks, the unit view directions)."""
+    contiguous rays, the t table, the uint8 grid, its macro blocks, the unit view directions).
+    With ``budget`` (needs return_used) the per-ray counts are also cut at that many points
+    (nerf_march_budget, enqueued before the march's one host read, whose spare slots carry its two
+    numbers: no further synchronisation): the result gains seg_off (int32 [N+1]), rays_kept, n_points."""
     rays = _f32c(rays.reshape(-1, 6), "rays")
     dev, N = rays.device, rays.shape[0]
     L = lib()
@@ -897,6 +901,8 @@ def _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd,
                "n_evaluated": 0, "rounds": 0}
         if return_used:
             out["ray_used"] = torch.zeros(0, dtype=torch.int32, device=dev)
+        if budget is not None:
+            out.update(seg_off=torch.zeros(1, dtype=torch.int32, device=dev), rays_kept=0, n_points=0)
         return out, None
     if t_table is None:
         t_table = device_table("arange", float(near), float(far), float(step_size), dev)
@@ -916,7 +922,8 @@ def _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd,
     off = torch.empty(N, dtype=torch.int32, device=dev)
     cnt = torch.empty(N, dtype=torch.int32, device=dev)
     counters = torch.zeros(2, dtype=torch.int32, device=dev)
-    stats = torch.zeros(2, dtype=torch.int64, device=dev)  # [0] composited (queried), [1] evaluated
+    # [0] composited (queried), [1] evaluated; with a budget also [2] rays kept, [3] their points
+    stats = torch.zeros(2 if budget is None else 4, dtype=torch.int64, device=dev)
     used = torch.zeros(N, dtype=torch.int32, device=dev) if return_used else None
     # the largest K times every ray, or the byte budget (a ray that does not fit waits a round)
     cap = max(1, min(N * max(k_schedule), round_bytes // MARCH_POINT_BYTES, 2 ** 31 - 1))
@@ -960,12 +967,17 @@ def _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd,
         if rounds % sync_every == 0 and int(counters[1]) == 0:
             break
     check(L.nerf_march_finish(ptr(rgb), ptr(acc), N, int(bool(white_bkgd)), s), "nerf_march_finish")
+    seg_off = None
+    if budget is not None:  # (before the host read below, which then brings its two numbers along)
+        seg_off, _ = march_budget(used, budget, keep=stats[2:])
     st = stats.tolist()
     live_rounds = int((live_hist[:rounds] > 0).sum())
     out = {"rgb_map_f": rgb, "depth_map_f": depth, "acc_map_f": acc, "n_queried": int(st[0]),
            "n_evaluated": int(st[1]), "rounds": live_rounds, "rounds_launched": rounds}
     if return_used:
         out["ray_used"] = used
+    if budget is not None:
+        out.update(seg_off=seg_off, rays_kept=int(st[2]), n_points=int(st[3]))
     return out, (rays, t_table, n_steps, g, res, macro, vd)
 
 
@@ -1022,10 +1034,31 @@ def march_segments(rays: torch.Tensor, t_table: torch.Tensor, grid_u8: torch.Ten
     return out_ray, out_step, out_pts
 
 
+def march_budget(ray_used: torch.Tensor, budget: int, keep: Optional[torch.Tensor] = None):
+    """Per-ray point counts (int32 [N]) -> the segment offsets of the longest prefix of rays whose
+    points fit in ``budget`` (nerf_march_budget, one launch): seg_off int32 [N+1] = the exclusive
+    prefix sum up to rays_kept, the kept points' total after it (dropped rays own empty segments),
+    and keep int64 [2] on the device = (rays_kept, their points).  ``keep`` may be two spare int64
+    slots of a tensor the caller reads back anyway; no host synchronisation here."""
+    if ray_used.dtype != torch.int32:
+        raise TypeError(f"ray_used must be int32, got {ray_used.dtype}")
+    ray_used = ray_used.contiguous()
+    N, dev = ray_used.numel(), ray_used.device
+    s = stream_of(ray_used)
+    seg_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    if keep is None:
+        keep = torch.empty(2, dtype=torch.int64, device=dev)
+    elif keep.dtype != torch.int64 or keep.numel() < 2 or not keep.is_contiguous() or keep.device != dev:
+        raise TypeError("keep must be a contiguous int64 tensor of at least 2 elements on ray_used's device")
+    check(lib().nerf_march_budget(ptr(ray_used) if N else None, N, int(budget), ptr(seg_off), keep.data_ptr(), s),
+          "nerf_march_budget")
+    return seg_off, keep
+
+
 def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: torch.Tensor,
                step_size: float = 0.005, t_thresh: float = 1e-4, bbox=SCENE_BBOX, white_bkgd: bool = True, dtype=F32,
                t_table: Optional[torch.Tensor] = None, k_schedule=(12, 24, 48, 96, 192, 384, 768),
-               round_bytes: int = 1 << 31, use_macro: bool = True):
+               round_bytes: int = 1 << 31, use_macro: bool = True, max_points: Optional[int] = None):
     """march() whose maps carry an autograd graph back to the packer's parameters: what the
     reference's render_accelerated gives when it is called with autograd on.  Two passes, in the
     spirit of the detached sample_pdf of render().  Pass A is march() itself, without gradient:
@@ -1035,22 +1068,44 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
     reservation: the sample order, and with it the dW sum order and the gradient, is the same
     run to run), runs the training MLP on them once, and composites every segment with a
     differentiable kernel pair.  M = n_queried comes from pass A's one host read; no other
-    host synchronisation.  Same keys as march(); M == 0 gives the background and zero gradients."""
+    host synchronisation.  Same keys as march(); M == 0 gives the background and zero gradients.
+
+    ``max_points=B`` bounds pass B: pass A still marches all N rays, nerf_march_budget cuts the
+    per-ray counts at the largest prefix of rays whose points fit in B, and pass B differentiates
+    through those ``rays_kept`` rays' ``n_points`` <= B points only -- the launches an unbudgeted call
+    on rays[:rays_kept] makes, so rows < rays_kept and their gradient equal that call's bit for bit.
+    The maps keep N rows: rows >= rays_kept hold pass A's values and carry no gradient.  n_queried
+    stays pass A's count over all N rays.  B must be at least the march's steps (a ray can need them
+    all), so that rays_kept >= 1 for N >= 1; the two numbers ride on pass A's host read."""
+    if max_points is not None:
+        max_points = int(max_points)
+        n_steps = (t_table.numel() if t_table is not None
+                   else _cpu_table("arange", float(near), float(far), float(step_size)).numel())
+        if not n_steps <= max_points <= 2 ** 31 - 1:
+            raise ValueError(f"march_grad: max_points must be in [{n_steps} (the march's steps: one ray can need "
+                             f"them all), 2^31 - 1], got {max_points}")
     with torch.no_grad():
         out, walk = _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table,
-                           k_schedule, round_bytes, 8, 0.9, 4, use_macro, True, 8, True)
+                           k_schedule, round_bytes, 8, 0.9, 4, use_macro, True, 8, True, max_points)
     used = out.pop("ray_used")
+    seg_off = out.pop("seg_off", None)
     if walk is None:  # no rays
         return out
     rays_c, t_tab, _, g8, _, macro, vd = walk
-    N, M = rays_c.shape[0], out["n_queried"]
-    seg_off = torch.zeros(N + 1, dtype=torch.int32, device=rays_c.device)
-    seg_off[1:] = torch.cumsum(used, 0, dtype=torch.int32)
+    N = rays_c.shape[0]
+    if max_points is None:
+        n_keep, M = N, out["n_queried"]
+        seg_off = torch.zeros(N + 1, dtype=torch.int32, device=rays_c.device)
+        seg_off[1:] = torch.cumsum(used, 0, dtype=torch.int32)
+    else:
+        n_keep, M = out["rays_kept"], out["n_points"]
+    if n_keep < N:  # pass B over the kept rays alone: the first n_keep + 1 offsets are their exclusive prefix sum
+        rays_c, vd = rays_c[:n_keep], vd[:n_keep]
     out_ray, out_step, out_pts = march_segments(rays_c, t_tab, g8, macro, seg_off, M, bbox)
     raw = mlp(packer, out_pts, vd, 1, out_ray, dtype)
-    rgb, depth, acc = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size),
-                                               bool(white_bkgd))
-    out.update(rgb_map_f=rgb, depth_map_f=depth, acc_map_f=acc)
+    maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd))
+    for k, v in zip(("rgb_map_f", "depth_map_f", "acc_map_f"), maps):
+        out[k] = v if n_keep == N else torch.cat([v, out[k][n_keep:]], 0)  # (the dropped rows: pass A's, no graph)
     return out
 
 

@@ -9,7 +9,9 @@ item is one whole image.  Pixel id = img*H*W + j*W + i, the reference's flatteni
 
 Deliberate difference: the reference draws ``cfg.train.batch_size`` (= 1) rays per step
 (blender.py:53,126) while its config's ``N_rays`` is unused; here a train batch has
-``cfg.task_arg.train_rays`` rays (default 4096, BASELINE config 3).
+``cfg.task_arg.train_rays`` rays (default 4096, BASELINE config 3).  ``batch_rays`` is that count and
+is read at every draw: with ``task_arg.point_budget`` the loss module rewrites it after each training
+step (src/train/trainers/nerf.py), and ``sample_batch(n_rays=)`` serves a caller that has no loader.
 """
 import json
 import os

@@ -48,6 +48,7 @@ class Renderer:
         self.resolution = None
         self.grid_resolution = None
         self.voxel_size = None
+        self.max_points = None  # task_arg.point_budget: the cap of a differentiable march (the loss module sets it)
         self._calls = 0
         rank = int(os.environ.get("RANK", "0"))
         self._seed = (torch.initial_seed() * 1000003 + rank * 7919) & ((1 << 63) - 1)
@@ -206,12 +207,25 @@ class Renderer:
     def _render_accelerated_grad(self, rays_flat, near, far):
         """render_accelerated under autograd (ops.march_grad): the maps carry a graph back to the fine
         net, as the reference's plain-torch march does.  Rays in chunks of task_arg.chunk_size,
-        concatenated, as render() does; no device-wide synchronisation (render_time is host time)."""
+        concatenated, as render() does; no device-wide synchronisation (render_time is host time).
+        With a point budget (self.max_points) the whole batch is ONE march instead: chunk_size does not
+        split it -- the differentiable pass is bounded by max_points and the no-grad pass by the march's
+        round_bytes -- and the result also carries rays_kept / n_points (ops.march_grad(max_points=))."""
         ta = cfg.task_arg
         start = time.time()
         chunk = self._chunk(True)
         packer = self.net.model_fine.packer()
         sched = tuple(int(k) for k in ta.get("train_k_schedule", TRAIN_K_SCHEDULE))
+        if self.max_points:
+            out = ops.march_grad(packer, rays_flat, near, far, self.occupancy_grid,
+                                 step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
+                                 bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
+                                 k_schedule=sched, max_points=int(self.max_points))
+            keys = ("rgb_map_f", "depth_map_f", "acc_map_f", "n_queried", "n_evaluated", "rounds", "rays_kept",
+                    "n_points")
+            ret = {k: out[k] for k in keys}
+            ret["render_time"] = time.time() - start
+            return ret
         maps = {"rgb_map_f": [], "depth_map_f": [], "acc_map_f": []}
         counts = {"n_queried": 0, "n_evaluated": 0, "rounds": 0}
         for i in range(0, rays_flat.shape[0], chunk):

@@ -19,6 +19,18 @@ march queries; the coarse net is not trained in this mode), updated from the liv
 (no grad) then also goes through render_accelerated with the live grid -- an untrained coarse
 net would make render()'s importance sampling meaningless -- with stats {loss_f, total_loss}.
 save_grid() / load_grid() write and read the grid beside the checkpoints (train.py).
+
+``task_arg.point_budget.target > 0`` (default 0: off; only with ``train_renderer: accelerated``, either
+``train_grid``) lets the ray count follow the occupancy: the module owns a RayBudget (``.ray_budget``),
+every training forward marches its whole batch as one call capped at ``max_points`` differentiated
+points (rays past the cap are marched but left out of the loss: MSE over the first ``rays_kept`` rows),
+reports stats {loss_f, total_loss, rays, points}, observes (rays marched, points queried) and sets the
+loader's dataset.batch_rays, so the batch Trainer.train_step prefetches next has the new count.  Without
+a loader the caller reads ``.ray_budget.rays``.  Validation is untouched.  Data parallel: every rank
+follows its own count with no collective, so the all-reduce averages per-rank MEAN gradients of
+different ray counts (each rank weighs 1 / world, not its rays); the online grids stay bit-identical
+(they depend on the weights only).  save_grid() / load_grid() also carry the count
+(<model_dir>/ray_budget_state.pt).
 """
 import os
 
@@ -29,11 +41,13 @@ from nerf_amd import ops
 
 from src.config import cfg
 from src.models.nerf.renderer.online_grid import OnlineGrid, grid_update_settings
+from src.models.nerf.renderer.ray_budget import RayBudget
 from src.models.nerf.renderer.volume_renderer import Renderer
 
 TRAIN_RENDERERS = ("hierarchical", "accelerated")
 TRAIN_GRIDS = ("file", "online")
 GRID_STATE_FILE = "occupancy_grid_state.pt"
+BUDGET_STATE_FILE = "ray_budget_state.pt"
 
 
 def occupancy_grid_path():
@@ -47,6 +61,7 @@ class NetworkWrapper(nn.Module):
     def __init__(self, net, train_loader=None):
         super().__init__()
         self.net = net
+        self.train_loader = train_loader
         self.renderer = Renderer(self.net)
         self.loss_fn = nn.MSELoss()
         self.train_renderer = str(cfg.task_arg.get("train_renderer", "hierarchical") or "hierarchical")
@@ -55,6 +70,10 @@ class NetworkWrapper(nn.Module):
         self.train_grid = str(cfg.task_arg.get("train_grid", "file") or "file")
         if self.train_grid not in TRAIN_GRIDS:
             raise ValueError(f"task_arg.train_grid must be one of {TRAIN_GRIDS}, got {self.train_grid!r}")
+        self.ray_budget = RayBudget.from_config(cfg.task_arg)  # (None: point_budget.target 0, the fixed train_rays)
+        if self.ray_budget is not None:
+            self.renderer.max_points = self.ray_budget.max_points
+            self._publish_rays()  # (train_rays clamped and rounded to the budget's bounds)
         self.online_grid = None
         if self.train_grid == "online":
             if self.train_renderer != "accelerated":
@@ -81,7 +100,11 @@ class NetworkWrapper(nn.Module):
     def save_grid(self, model_dir):
         """Online mode, beside a checkpoint: logs/<cfg name>/occupancy_grid.pt in occupancy_grid.py's bool
         format (run.py evaluate and render_video.py load it) and <model_dir>/occupancy_grid_state.pt
-        (density, counters, settings: what a resumed run continues from).  A no-op in file mode."""
+        (density, counters, settings: what a resumed run continues from); a no-op in file mode.  With a
+        point budget also <model_dir>/ray_budget_state.pt (the ray count a resumed run continues at)."""
+        if self.ray_budget is not None:
+            os.makedirs(model_dir, exist_ok=True)
+            torch.save(self.ray_budget.state_dict(), os.path.join(model_dir, BUDGET_STATE_FILE))
         if self.online_grid is None:
             return
         path = occupancy_grid_path()
@@ -91,7 +114,13 @@ class NetworkWrapper(nn.Module):
         torch.save(self.online_grid.state_dict(), os.path.join(model_dir, GRID_STATE_FILE))
 
     def load_grid(self, model_dir):
-        """Resume: the state save_grid wrote, when it is there.  True when it was loaded."""
+        """Resume: the state save_grid wrote, when it is there.  True when the grid was loaded.  The ray
+        budget's count is read the same way; without its file the run starts from train_rays."""
+        path = os.path.join(model_dir, BUDGET_STATE_FILE)
+        if self.ray_budget is not None and os.path.exists(path):
+            self.ray_budget.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+            self._publish_rays()
+            print(f"load ray budget state: {path} ({self.ray_budget.rays} rays)")
         path = os.path.join(model_dir, GRID_STATE_FILE)
         if self.online_grid is None or not os.path.exists(path):
             return False
@@ -99,8 +128,26 @@ class NetworkWrapper(nn.Module):
         print(f"load occupancy grid state: {path}")
         return True
 
+    def _publish_rays(self):
+        """The budget's ray count to the loader's dataset: the next batch drawn has that many rays."""
+        if self.train_loader is not None:
+            self.train_loader.dataset.batch_rays = self.ray_budget.rays
+
+    def _budgeted_step(self, batch, gt):
+        """The training forward under a point budget: one capped march, the loss over the kept rays, then the
+        observation of ALL marched rays (the dropped ones were marched too) that sets the next count."""
+        ret = self.renderer.render_accelerated(batch)
+        kept, n = ret["rays_kept"], ret["rgb_map_f"].shape[0]
+        loss_f, _, total = ops.mse_pair(ret["rgb_map_f"][:kept], None, gt[:kept])
+        self.ray_budget.observe(n, ret["n_queried"])
+        self._publish_rays()
+        # (host tensors: a device scalar per step would be a blocking pageable copy, ops.device_scalar)
+        return ret, total, {"loss_f": loss_f, "total_loss": total, "rays": torch.tensor(float(n)),
+                            "points": torch.tensor(float(ret["n_points"]))}
+
     def forward(self, batch):
         gt = batch["rgbs"].reshape(-1, 3) if batch["rgbs"].dim() == 3 else batch["rgbs"]
+        budgeted = self.ray_budget is not None and torch.is_grad_enabled()
         if self.online_grid is not None:
             grid = self._live_grid(batch["rays"].device)
             fine = self.net.model_fine
@@ -108,9 +155,13 @@ class NetworkWrapper(nn.Module):
                 grid.step(fine.packer(), self.net.mlp_dtype)  # (may update; update 0 precedes the first march)
             elif grid.updates == 0:  # validation before any training step: never march the all-ones grid
                 grid.update(fine.packer(), self.net.mlp_dtype)
+            if budgeted:
+                return self._budgeted_step(batch, gt)
             ret = self.renderer.render_accelerated(batch)
             loss_f, _, total = ops.mse_pair(ret["rgb_map_f"], None, gt)
             return ret, total, {"loss_f": loss_f, "total_loss": total}
+        if budgeted:
+            return self._budgeted_step(batch, gt)
         if self.train_renderer == "accelerated" and torch.is_grad_enabled():
             # the fine net through the grid march; the MSE and its backward in one launch each
             # (ops.mse_pair with no second image)

@@ -43,7 +43,8 @@ def train(cfg, network):
     evaluator = make_evaluator(cfg)
     begin_epoch = load_model(network, optimizer, scheduler, recorder, cfg.trained_model_dir, resume=cfg.resume)
     # task_arg.train_grid: online -- the trainer's occupancy grid travels beside the checkpoints (the loss
-    # module's save_grid / load_grid; both are no-ops in file mode)
+    # module's save_grid / load_grid; both are no-ops in file mode).  The same two calls carry the ray count of
+    # task_arg.point_budget (ray_budget_state.pt), so a resumed run continues at its count
     loss_module = trainer.network
     if begin_epoch > 0 and hasattr(loss_module, "load_grid"):
         loss_module.load_grid(cfg.trained_model_dir)
