@@ -35,6 +35,10 @@ extern "C" {
 
 #define NERF_MLP_STORE 1   /* keep activations + ReLU masks for backward */
 #define NERF_MLP_DENSITY 2 /* sigma only (grid bake) */
+/* dtype 0 with NERF_MLP_STORE only (-22 otherwise): run the 32x32x2 fp32 training forward instead of the default
+ * wide 16x16x4 one.  Both read the same forward pack and write the same bits (raw, act, masks); this one is the
+ * reference of the bitwise test and the A/B arm of tools/mlp_bench.py.  (Added within ABI 4.) */
+#define NERF_MLP_F32_NARROW 4
 
 const char* nerf_last_error(void);
 int nerf_abi_version(void);

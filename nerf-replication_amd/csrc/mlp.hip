@@ -61,10 +61,12 @@ struct PF32 {
   static constexpr int PE = 1;  // PE_LIBM: the fp32 parity path (pe_trig)
   using Store = float;
   struct Tile { float v[16]; };
+  // (a packed 16-byte slot holds its four weights in the order rho 4c + 0, 2, 1, 3 -- rho_of below: the wide fp32
+  // forward, PF32W, then reads its pair of one slot as 8 aligned bytes; here the order is a renaming of a's fields)
   static __device__ __forceinline__ f32x16 mma(uint4 a, const Tile& b, int c, f32x16 acc) {
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), b.v[4 * c + 0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), b.v[4 * c + 1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), b.v[4 * c + 2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), b.v[4 * c + 1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), b.v[4 * c + 2], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), b.v[4 * c + 3], acc, 0, 0, 0);
     return acc;
   }
@@ -77,7 +79,7 @@ struct PF32 {
   static __device__ __forceinline__ float get(const Tile& t, int rho) { return t.v[rho]; }
   static __device__ __forceinline__ Store cvt(float x) { return x; }
   // packed weight element e of chunk c: accumulator register (k order) and stored value
-  static __host__ __device__ constexpr int rho_of(int c, int e) { return c * E + e; }
+  static __host__ __device__ constexpr int rho_of(int c, int e) { return c * E + (e == 1 ? 2 : e == 2 ? 1 : e); }
   static __device__ __forceinline__ Store cvt_c(float x, int) { return x; }
   static __device__ __forceinline__ f32x16 mma_k(uint4 a, uint4 b, f32x16 acc) {
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
@@ -328,16 +330,29 @@ struct PBF3W {
   // packed weight element e of chunk c, lane group g: feature k16_feat(g, e) of the K-block, split part c
   static __host__ __device__ constexpr int feat16(int, int g, int e) { return k16_feat(g, e); }
   static __host__ __device__ constexpr int part16(int c) { return c; }
+  // forward B operand: the feature of a K-block in register e of lane group g
+  static __host__ __device__ constexpr int fwd_feat(int g, int e) { return k16_feat(g, e); }
 };
 
 // The wide fp32 TRAINING forward (round 6, PF32W): the PBF3W structure on v_mfma_f32_16x16x4_f32 -- one wave =
 // 16 samples, 8 waves per workgroup, two per SIMD (the 32x32x2 fp32 forward holds 32 samples' fp32 tiles in
-// ~450 registers: one wave per SIMD).  A K-block (32 features x 16 samples) is 8 MFMAs; MFMA j's B operand in
-// lane (s, g) is feature 16 (j >> 2) + 4 g + (j & 3) = k16_feat(g, j), so a 16x16 output tile mt (rows 4 g + e
-// in lane g) IS registers 4 (mt & 1) + e of the next layer's K-block mt >> 1.  Chunk c (1 KiB) of a K-block =
-// MFMAs 4c .. 4c + 3: lane l = r16 + 16 g reads W[r16][16 c + 4 g + 0..3], four contiguous fp32.  Same
-// arithmetic as PF32 (fp32 products, fp32 accumulation, libm PE), another summation order: the training forward
-// only -- renders keep PF32's order, which the full-frame fixtures are pinned against.
+// ~450 registers: one wave per SIMD).  A K-block (32 features x 16 samples) is 8 MFMAs, and a 16x16 output tile
+// mt (rows 4 g + e in lane group g) IS registers 4 (mt & 1) + e of the next layer's K-block mt >> 1.
+//
+// The FORWARD (round 7) sums in PF32's order and is bit-identical to it -- raw, stored activations, masks.  Both
+// f32 MFMAs are a k-ordered fmaf chain (the 32x32x2 over its two lane halves, the 16x16x4 over its four lane
+// groups), so MFMA j's B operand in lane (s, g) is feature f32w_feat(g, j) (mlp_tables.h): positions 4 j + g of
+// PF32's K sequence 0,4,1,5,2,6,3,7, 8,12,...  The weight rows of a 16-row unit are permuted to match (f32w_row),
+// which costs nothing: the kernel reads PF32's own forward pack (DIR 0, no second pack) and the permutation is
+// which bytes a lane fetches.  PF32's 16-byte slot (row r, half h, chunk b) holds rho = 4b + 0, 2, 1, 3; lane
+// (r16, g) needs rho 4b + (g >> 1) and 4b + 2 + (g >> 1) of half g & 1 for MFMAs 2b, 2b + 1: one aligned
+// ds_read_b64 at 16 (32 (g & 1) + row) + 8 (g >> 1) of the chunk.  A step (t, c) is the four MFMAs 4c .. 4c + 3 =
+// PF32's chunks 2c, 2c + 1.  (The two lane groups of a half-wave read the same 8 bytes of the slots of both
+// halves h: a 2-way LDS bank conflict, 4 LDS cycles per read instead of 2 -- 16 cycles per 256 MFMA cycles and
+// wave.  It is inherent in a 16-byte slot that PF32 reads whole)
+//
+// The wide dX keeps its own DIR 3 pack and K order, feat16 = 16 c + 4 g + e (it flips no ReLU branch).
+// The training forward only -- renders keep the 32x32 PF32 kernels (a follow-up with its own measurement).
 struct PF32W {
   static constexpr int KIND = K_F32W;
   using Acc = f32x4;
@@ -358,8 +373,9 @@ struct PF32W {
   }
   static __host__ __device__ constexpr int rho_of(int c, int e) { return 4 * c + e; }
   static __device__ __forceinline__ Store cvt_c(float x, int) { return x; }
-  static __host__ __device__ constexpr int feat16(int c, int g, int e) { return 16 * c + 4 * g + e; }
+  static __host__ __device__ constexpr int feat16(int c, int g, int e) { return 16 * c + 4 * g + e; }  // (the dX pack)
   static __host__ __device__ constexpr int part16(int) { return 0; }
+  static __host__ __device__ constexpr int fwd_feat(int g, int e) { return f32w_feat(g, e); }  // (the forward: PF32's order)
 };
 // The wide bf16 dX (round 6, PBF16W): the bf16 dX of the bf16 and bf16x3f tiers on v_mfma_f32_16x16x32_bf16 over the
 // 16-row W^T units -- PBF3W's layout with the hi half only (one 1 KiB chunk per K-block).
@@ -428,8 +444,24 @@ constexpr int M_ALIGN = 256;  // activation stores are padded to this many sampl
 // ------------------------------------------------------------------------------------
 // DIR 0: forward units, 1: dX-chain units, 2: 16-row forward units (PBF3W)
 // DIR 3: 16-row dX units (PF32W / PBF3W)
+// DIR 4: the 16-row forward units of DIR 2 computed from the DIR 0 pack of PF32 (the wide fp32 forward, PF32W):
+//        the two 16-row units 2n, 2n + 1 of a layer are the row halves of 32-row unit n and share its chunks
+constexpr int DIR_F32W = 4;
 __host__ __device__ constexpr int num_units(int dir) {
-  return dir == 0 ? NUNIT_FWD : dir == 1 ? NUNIT_BWD : dir == 2 ? NUNIT_FWD16 : NUNIT_BWD16;
+  return dir == 0 ? NUNIT_FWD : dir == 1 ? NUNIT_BWD : (dir == 2 || dir == DIR_F32W) ? NUNIT_FWD16 : NUNIT_BWD16;
+}
+// DIR 4: the 32-row unit (of DIR 0) that holds 16-row unit u, and the 16-row units of a 32-row unit
+__host__ __device__ constexpr int f32w_unit32(int u) {
+  const int L = fwd16_unit_layer(u);
+  return fwd_unit_first(L) + ((u - fwd16_unit_first(L)) >> 1);
+}
+__host__ __device__ constexpr int f32w_unit16_first(int u32) {
+  const int L = fwd_unit_layer(u32);
+  return fwd16_unit_first(L) + 2 * (u32 - fwd_unit_first(L));
+}
+__host__ __device__ constexpr int f32w_unit16_count(int u32) {
+  const int L = fwd_unit_layer(u32);
+  return L == LRGB || (L == LFA && u32 - fwd_unit_first(L) == 8) ? 1 : 2;  // (all-padding row halves are skipped)
 }
 __host__ __device__ constexpr int fwd_unit_chunks(int u, int ch) { return fwd_unit_tiles(u) * ch + 1; }
 __host__ __device__ constexpr int fwd16_unit_chunks(int u, int ch) { return fwd16_unit_tiles(u) * ch + 1; }
@@ -717,7 +749,8 @@ __host__ __device__ constexpr bool unit_used(int u) {
                    : (u < fwd16_unit_first(LFA) || u == fwd16_unit_first(LFA) + 16));
 }
 template <int DIR> __host__ __device__ constexpr int unit_seg(int u) {
-  return DIR == 0 ? fwd_unit_layer(u) : DIR == 1 ? bwd_unit_stage(u) : DIR == 2 ? fwd16_unit_layer(u) : bwd16_unit_stage(u);
+  return DIR == 0 ? fwd_unit_layer(u) : DIR == 1 ? bwd_unit_stage(u)
+       : (DIR == 2 || DIR == DIR_F32W) ? fwd16_unit_layer(u) : bwd16_unit_stage(u);
 }
 template <int DIR> __host__ __device__ constexpr int unit_chunks(int u, int ch) {
   return DIR == 0 ? fwd_unit_chunks(u, ch) : DIR == 1 ? bwd_unit_chunks(u, ch)
@@ -734,6 +767,16 @@ struct Groups {
   Group g[NUNIT_MAX];
   int n;
   __host__ __device__ constexpr Groups() : g(), n(0) {
+    if (DIR == DIR_F32W) {
+      // PF32's own groups (its pack, its slots, its chunk count), each 32-row unit as its one or two 16-row units
+      const Groups<0, DENSITY, PF32::CH> T0{};
+      for (int i = 0; i < T0.n; ++i) {
+        Group G{f32w_unit16_first(T0.g[i].u0), 0, T0.g[i].c0, T0.g[i].nch};
+        for (int j = 0; j < T0.g[i].n; ++j) G.n += f32w_unit16_count(T0.g[i].u0 + j);
+        g[n++] = G;
+      }
+      return;
+    }
     const int NU = num_units(DIR);
     int u = 0;
     while (u < NU) {
@@ -802,7 +845,8 @@ __host__ __device__ constexpr int handoff_vmcnt(int g, StoresFn stores, int prol
 
 struct Step { int j, u, t, c, off, kin, len; bool first, last; };
 template <int DIR> __host__ __device__ constexpr int unit_tiles(int u) {
-  return DIR == 0 ? fwd_unit_tiles(u) : DIR == 1 ? bwd_unit_tiles(u) : DIR == 2 ? fwd16_unit_tiles(u) : bwd16_unit_tiles(u);
+  return DIR == 0 ? fwd_unit_tiles(u) : DIR == 1 ? bwd_unit_tiles(u)
+       : (DIR == 2 || DIR == DIR_F32W) ? fwd16_unit_tiles(u) : bwd16_unit_tiles(u);
 }
 template <int DIR, bool DENSITY, int CH>
 __host__ __device__ constexpr int group_steps(int g) {
@@ -818,6 +862,12 @@ __host__ __device__ constexpr Step group_step(int g, int k) {
     const int u = G.u0 + j, n = unit_tiles<DIR>(u) * CH;
     if (k < n) {
       const int t = k / CH, c = k % CH;
+      if (DIR == DIR_F32W) {
+        // off in 256-byte units: PF32's chunks 2c, 2c + 1 of tile t of the 32-row unit, + 256 B for its upper 16 rows
+        const int u32 = f32w_unit32(u), hi = (u - fwd16_unit_first(fwd16_unit_layer(u))) & 1;
+        const int ch = fwd_unit_chunk_off(u32, PF32::CH) - G.c0 + PF32::CH * t + 2 * c;
+        return Step{j, u, t, c, 4 * ch + hi, k, n, k == 0, k == n - 1};
+      }
       return Step{j, u, t, c, unit_chunk_off<DIR>(u, CH) - G.c0 + k, k, n, k == 0, k == n - 1};
     }
     k -= n;
@@ -1027,19 +1077,19 @@ __host__ __device__ constexpr int bwd_out_slot(int s, int j) {
 template <int DIR> __host__ __device__ constexpr int unit_in_slot(int u, int t) {
   return DIR == 0 ? fwd_in_slot(fwd_unit_layer(u), t)
        : DIR == 1 ? bwd_in_slot(bwd_unit_stage(u), t)
-       : DIR == 2 ? fwd_in_slot(fwd16_unit_layer(u), t)
+       : (DIR == 2 || DIR == DIR_F32W) ? fwd_in_slot(fwd16_unit_layer(u), t)
        : bwd_in_slot(bwd16_unit_stage(u), t);
 }
 // 16-row unit (DIR 2): output tile m fills half m & 1 (elements 4 (m & 1) .. + 3) of K-block slot m >> 1
 template <int DIR> __host__ __device__ constexpr int unit_out_slot(int u) {
   return DIR == 0 ? fwd_out_slot(fwd_unit_layer(u), u - fwd_unit_first(fwd_unit_layer(u)))
        : DIR == 1 ? bwd_out_slot(bwd_unit_stage(u), u - bwd_unit_first(bwd_unit_stage(u)))
-       : DIR == 2 ? fwd_out_slot(fwd16_unit_layer(u), (u - fwd16_unit_first(fwd16_unit_layer(u))) >> 1)
+       : (DIR == 2 || DIR == DIR_F32W) ? fwd_out_slot(fwd16_unit_layer(u), (u - fwd16_unit_first(fwd16_unit_layer(u))) >> 1)
        : bwd_out_slot(bwd16_unit_stage(u), (u - bwd16_unit_first(bwd16_unit_stage(u))) >> 1);
 }
 // the register pairs of its slot a unit's finish writes (a 32x32 tile: all 8; a 16-row unit: 2 of a K-block's 4)
 template <int DIR> __host__ __device__ constexpr int unit_out_pairs(int u) {
-  return DIR == 2 ? (((u - fwd16_unit_first(fwd16_unit_layer(u))) & 1) ? 0xC : 0x3)
+  return (DIR == 2 || DIR == DIR_F32W) ? (((u - fwd16_unit_first(fwd16_unit_layer(u))) & 1) ? 0xC : 0x3)
        : DIR == 3 ? (((u - bwd16_unit_first(bwd16_unit_stage(u))) & 1) ? 0xC : 0x3) : 0xFF;
 }
 // register pairs (bit k = registers 2k, 2k + 1) of a tile that MFMA chunk c reads / finish part p writes
@@ -1175,8 +1225,32 @@ struct FinishSchedule {
     return 0;
   }
 };
+// (PF32W's 16-row forward units, DIR 2, run over PF32's pack: their groups and steps are DIR 4's)
+template <class P, int DIR> __host__ __device__ constexpr int sched_dir() {
+  return P::KIND == K_F32W && DIR == 2 ? DIR_F32W : DIR;
+}
 template <class P, int DIR, bool DENSITY> __host__ __device__ constexpr int finish_schedule_violation() {
-  return FinishSchedule<P, DIR, DENSITY>{}.violation;
+  return FinishSchedule<P, sched_dir<P, DIR>(), DENSITY>{}.violation;
+}
+
+// the A operand of one step from the current slot (wl: this lane's base in it; OFF: Step::off).  DIR 4: the 8 bytes
+// of this lane's half of two of PF32's 16-byte slots, chunks 2c and 2c + 1 (OFF in 256-byte units)
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// (Relaxed wavefront-scope atomic loads: two plain ds_read_b64, 2 LDS cycles each on 64 banks, 4 with this layout's
+// 2-way conflict, and no memory-model wait behind them.  Plain loads hipcc pairs into ds_read2st64_b64 /
+// ds_read2_b64, which bank on 32 and take twice the LDS cycles; volatile ones it follows with lgkmcnt(0) each,
+// which undoes the prefetch.)
+typedef __attribute__((address_space(3))) uint64_t lds_u64;
+template <int DIR, int OFF>
+__device__ __forceinline__ uint4 load_a(lds_cu4* wl) {
+  if constexpr (DIR == DIR_F32W) {
+    lds_u64* p = (lds_u64*)wl;
+    const uint64_t lo = __hip_atomic_load(p + OFF * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    const uint64_t hi = __hip_atomic_load(p + OFF * 32 + 128, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+  } else {
+    return as_uint4(wl[OFF * 64]);
+  }
 }
 
 // W: the wave object; it provides in_tile<u, t>(), prefetch<u>() (issue unit u's side
@@ -1197,7 +1271,7 @@ __device__ __forceinline__ void group_body(W& w, lds_cu4* wl) {
   sfor<(NS < PDP ? NS : PDP)>([&](auto kk) {
     constexpr int k = decltype(kk)::value;
     constexpr Step S = group_step<DIR, DENSITY, P::CH>(g, k);
-    ring[k] = as_uint4(wl[S.off * 64]);
+    ring[k] = load_a<DIR, S.off>(wl);
   });
   w.template prefetch<G.u0>();
   typename P::Acc acc;
@@ -1213,8 +1287,12 @@ __device__ __forceinline__ void group_body(W& w, lds_cu4* wl) {
     const uint4 a = ring[k % PDP];
     if constexpr (k + PDP < NS) {
       constexpr Step N = group_step<DIR, DENSITY, P::CH>(g, k + PDP);
-      ring[k % PDP] = as_uint4(wl[N.off * 64]);
+      ring[k % PDP] = load_a<DIR, N.off>(wl);
     }
+    // (PF32W forward, 240 of its 256 VGPRs: hipcc sinks each prefetched read to just before its MFMAs and waits
+    // lgkmcnt(0) there.  No MFMA or LDS read may cross this point -- 0x276: VALU, SALU, VMEM, LDS writes may --
+    // so the reads of step k + PDP are in flight over the MFMAs of step k.)
+    if constexpr (DIR == DIR_F32W) __builtin_amdgcn_sched_barrier(0x276);
     if constexpr (S.first) {
       if constexpr (S.j > 0) w.pend = acc;
       w.template init<S.u>(acc);
@@ -1776,8 +1854,9 @@ __device__ __forceinline__ void set_dword8(bf16x8& v, int k, uint32_t d) {
   else u.w = d;
   v = __builtin_bit_cast(bf16x8, u);
 }
-// position encoding of K-block TILE in the PBF3W B-operand layout: element e of lane group g is feature
-// 32 TILE + k16_feat(g, e); the same fp32 values as pe_tile<PBF3> (PE_POLY), split hi / lo
+// position encoding of K-block TILE in the wide B-operand layout: element e of lane group g is feature
+// 32 TILE + P::fwd_feat(g, e) (PBF3W: k16_feat, PF32W: f32w_feat); the same fp32 values as pe_tile<PBF3>
+// (PE_POLY), split hi / lo, or as pe_tile<PF32> (PE_LIBM)
 template <class T> __device__ __forceinline__ T sel4(int g, T a0, T a1, T a2, T a3) {
   return (g & 2) ? ((g & 1) ? a3 : a2) : ((g & 1) ? a1 : a0);  // (branch-free selects on the lane group)
 }
@@ -1787,10 +1866,10 @@ __device__ __forceinline__ void pe_kblock(typename P::Tile& t, int g, float x0, 
   float v[8];
   sfor<8>([&](auto ee) {
     constexpr int e = decltype(ee)::value;
-    constexpr PeFeat F0 = pe_feat(32 * TILE + k16_feat(0, e), NFREQ, NVALID);
-    constexpr PeFeat F1 = pe_feat(32 * TILE + k16_feat(1, e), NFREQ, NVALID);
-    constexpr PeFeat F2 = pe_feat(32 * TILE + k16_feat(2, e), NFREQ, NVALID);
-    constexpr PeFeat F3 = pe_feat(32 * TILE + k16_feat(3, e), NFREQ, NVALID);
+    constexpr PeFeat F0 = pe_feat(32 * TILE + P::fwd_feat(0, e), NFREQ, NVALID);
+    constexpr PeFeat F1 = pe_feat(32 * TILE + P::fwd_feat(1, e), NFREQ, NVALID);
+    constexpr PeFeat F2 = pe_feat(32 * TILE + P::fwd_feat(2, e), NFREQ, NVALID);
+    constexpr PeFeat F3 = pe_feat(32 * TILE + P::fwd_feat(3, e), NFREQ, NVALID);
     // every candidate is chosen at compile time; only the lane group selects among them
     const float c0 = F0.dim == 0 ? x0 : F0.dim == 1 ? x1 : x2, c1 = F1.dim == 0 ? x0 : F1.dim == 1 ? x1 : x2;
     const float c2 = F2.dim == 0 ? x0 : F2.dim == 1 ? x1 : x2, c3 = F3.dim == 0 ? x0 : F3.dim == 1 ? x1 : x2;
@@ -1841,7 +1920,10 @@ struct FwdWave16 {
   // with the halves exchanged by v_permlane32_swap -- bit-identical, bf16x3f training forward 1.502 -> 1.573 ms,
   // bf16x3 1.660 -> 1.769; profiles/r6/pair_store_ab.json)
   static constexpr int PRO_ST = NERF_DIAG_NO_ACT ? 0 : 6 * SST;  // the prologue's PE stores (3 K-blocks x 2 halves)
-  using GT = GroupTable<2, DENSITY, P::CH>;
+  // the units' layout in the pack and the slots: DIR 2, or (PF32W) DIR 4 -- the same 16-row units over PF32's pack
+  static constexpr int DIR = sched_dir<P, 2>();
+  static_assert(!F32 || (P::CH == 2 && PF32::CH == 4), "a PF32W step is two of PF32's four chunks");
+  using GT = GroupTable<DIR, DENSITY, P::CH>;
   static_assert(finish_schedule_violation<P, 2, DENSITY>() == 0,
                 "finish placement (NERF_FINISH_PARTS_* / NERF_FINISH_DELAY) reads a tile pair before its finish part "
                 "writes it, or reads a reassigned pend (FinishSchedule)");
@@ -1854,13 +1936,15 @@ struct FwdWave16 {
   uint32_t st_off;  // byte offset of this lane's 8 bytes in a 1-KiB chunk of the stores (PF32W: its 16 bytes,
                     // + 1 KiB (g >> 1): chunk 2 (mt & 1) + (g >> 1) of the fp32 tile-block)
   uint32_t lold;    // old-layout lane of the mask store: sample (16 (wave & 1) + s) + 32 (g & 1)
-  uint32_t gsh;     // 2 (g >> 1): offset of this lane's mask bits among an old register pair group
+  uint32_t gsh;     // 2 (g >> 1): offset of this lane's mask bits among an old register pair group (PF32W: 16 (g >> 1))
+  uint32_t a_off;   // byte offset of this lane's A operand in a chunk: 16 lane, or (PF32W) its 8 bytes of PF32's slot
+                    // (row f32w_row(lane & 15), half g & 1): 16 (32 (g & 1) + row) + 8 (g >> 1)
   float px, py, pz, dx, dy, dz;
   Tile X[2], D, Ha[8], Hb[8];
   uint32_t mw[4];
   uint32_t one16;
   float alpha, rgb0, rgb1, rgb2;
-  lds_cu4* wbg;     // current group's slot + 16 g (bias reads)
+  lds_cu4* wbg;     // current group's slot + 16 g (bias reads; PF32W: + 16 (g & 1) + 4 (g >> 1))
   uint4 bias;
   Acc pend;
   DmaLean dl;
@@ -1876,7 +1960,11 @@ struct FwdWave16 {
     const uint32_t sb = 16u * (uint32_t)(wave & 1) + (uint32_t)s;
     lold = sb + 32u * (uint32_t)(g & 1);
     st_off = 16u * lold + (F32 ? 1024u : 8u) * (uint32_t)(g >> 1);
-    gsh = 2u * (uint32_t)(g >> 1);
+    gsh = (F32 ? 16u : 2u) * (uint32_t)(g >> 1);
+    // f32w_row(a) of a = lane & 15 (mlp_tables.h), bit by bit: 8 (a >> 1 & 1) + 4 (a >> 2 & 1) + 2 (a & 1) + (a >> 3)
+    const uint32_t arow = 8u * ((uint32_t)(s >> 1) & 1u) + 4u * ((uint32_t)(s >> 2) & 1u) + 2u * ((uint32_t)s & 1u) +
+                          ((uint32_t)s >> 3);
+    a_off = F32 ? 16u * (32u * (uint32_t)(g & 1) + arow) + 8u * (uint32_t)(g >> 1) : 16u * (uint32_t)lane;
     one16 = opaque_one16();
     dl = DmaLean{a.wpack, (uint32_t)(lane * 16 + wave * 1024),
                  (uint32_t)__builtin_amdgcn_readfirstlane(lds_base + (uint32_t)wave * 1024u),
@@ -1915,7 +2003,7 @@ struct FwdWave16 {
   static __host__ __device__ constexpr int group_stores(int gi) {
     int n = 0;
     for (int u = 0; u < NUNIT_FWD16; ++u)
-      if (finished_in_group<2, DENSITY, P::CH, cross_finish<P, 2>()>(gi, u)) n += unit_stores(u);
+      if (finished_in_group<DIR, DENSITY, P::CH, cross_finish<P, DIR>()>(gi, u)) n += unit_stores(u);
     return n;
   }
   // the training stores of one 32-feature tile (a K-block, or the two 16-row tiles that fill it): old
@@ -1926,13 +2014,19 @@ struct FwdWave16 {
     store8(base, h0, h1);
     if constexpr (!HALF) store8(base + 2048, l0, l1);
   }
-  // PF32W: output-tile half hf of fp32 tile tau (values v[4 hf .. 4 hf + 3]) = old lane lold's 16 bytes of chunk
-  // 2 hf + (g >> 1) (old register rho = 4 (2 hf + (g >> 1)) + e holds feature 16 hf + 4 g + e, acc_row)
+  // PF32W: output-tile half hf of fp32 tile tau (values v[4 hf + e]).  Value e is feature 16 hf + f32w_feat(g, e) =
+  // old register rho = 4 (2 hf + (e >> 1)) + 2 (e & 1) + (g >> 1) of old lane lold: lanes (s, g) and (s, g ^ 2) --
+  // l and l ^ 32 -- hold elements {0, 2} and {1, 3} of the same two 16-byte pieces, chunks 2 hf and 2 hf + 1.  Two
+  // v_permlane32_swap (on copies: the K-block keeps its order for the next layer's MFMAs) give the lower lane
+  // the whole of piece 2 hf and the upper one the whole of 2 hf + 1 = chunk 2 hf + (g >> 1), st_off's.
   __device__ __forceinline__ void store_f32(int tau, int hf, const Tile& t) {
     if constexpr (NERF_DIAG_NO_ACT) return;
     char* base = (char*)a.act + (((wb32 * AT_TILES + tau) * SCH + 2 * hf) << 10) + st_off;
-    store16<0>((uint4*)base, make_uint4(__float_as_uint(t.v[4 * hf]), __float_as_uint(t.v[4 * hf + 1]),
-                                        __float_as_uint(t.v[4 * hf + 2]), __float_as_uint(t.v[4 * hf + 3])));
+    const auto r0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(t.v[4 * hf]), __float_as_uint(t.v[4 * hf + 2]),
+                                                     false, false);
+    const auto r1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(t.v[4 * hf + 1]), __float_as_uint(t.v[4 * hf + 3]),
+                                                     false, false);
+    store16<0>((uint4*)base, make_uint4(r0[0], r0[1], r1[0], r1[1]));
   }
   __device__ __forceinline__ void store_kblock(int tau, const Tile& t) {
     if constexpr (F32) {
@@ -1954,9 +2048,19 @@ struct FwdWave16 {
     return slot<fwd_in_slot(layer_of<u>(), t)>();
   }
   // the unit's bias chunk (rows 4 g + {0..3} = lane g) is the MFMA chain's initial accumulator, read one unit ahead
+  // (PF32W: PF32's bias chunk of the 32-row unit holds row r at float r; rows 16 (mt & 1) + f32w_row(4 g + e) =
+  // floats 16 (mt & 1) + 4 (g & 1) + (g >> 1) + {0, 2, 8, 10})
   template <int u> __device__ __forceinline__ void prefetch() {
-    constexpr int BOFF = unit_chunk_off<2>(u, CH) - GT::t.g[group_of<u>()].c0 + fwd_in_tiles(layer_of<u>()) * CH;
-    bias = as_uint4(wbg[BOFF * 64]);
+    if constexpr (F32) {
+      constexpr int u32 = f32w_unit32(u);
+      constexpr int BOFF = fwd_unit_chunk_off(u32, PF32::CH) - GT::t.g[group_of<u>()].c0 + fwd_in_tiles(layer_of<u>()) * PF32::CH;
+      typedef __attribute__((address_space(3))) const uint32_t lds_cu1;
+      lds_cu1* bp = (lds_cu1*)wbg + BOFF * 256 + 16 * (tile_of<u>() & 1);
+      bias = make_uint4(bp[0], bp[2], bp[8], bp[10]);
+    } else {
+      constexpr int BOFF = unit_chunk_off<2>(u, CH) - GT::t.g[group_of<u>()].c0 + fwd_in_tiles(layer_of<u>()) * CH;
+      bias = as_uint4(wbg[BOFF * 64]);
+    }
   }
   template <int u> __device__ __forceinline__ void init(Acc& acc) {
     constexpr int L = layer_of<u>(), mt = tile_of<u>();
@@ -1998,9 +2102,9 @@ struct FwdWave16 {
           y1 = __int_as_float(max(__float_as_int(y1), 0));
         }
         if constexpr (F32) {
-          // bits k / 16 + k: the pair's values non-zero (after the ReLU: > 0), the bf16 path's bit layout
+          // bits 2k, 2k + 1: the pair's values non-zero (after the ReLU: > 0)
           if constexpr (STORE && RELU && !NERF_DIAG_NO_MASK)
-            bits |= (min((uint32_t)__float_as_int(y0), 1u) | (min((uint32_t)__float_as_int(y1), 1u) << 16)) << k;
+            bits |= (min((uint32_t)__float_as_int(y0), 1u) | (min((uint32_t)__float_as_int(y1), 1u) << 1)) << (2 * k);
           out.v[2 * Q + 2 * k] = y0;
           out.v[2 * Q + 2 * k + 1] = y1;
         } else {
@@ -2016,6 +2120,8 @@ struct FwdWave16 {
         if constexpr (RELU && !NERF_DIAG_NO_MASK) {
           // value 2k + j of this lane = old register rho = 4 (2 (mt & 1) + (g >> 1)) + 2k + j of old tile n, old
           // lane half h = g & 1: mask bit 8 (n & 1) + (rho >> 1) + 16 (rho & 1) = [bit k / 16 + k] << (C + gsh)
+          // (PF32W: value e = old register rho = 4 (2 (mt & 1) + (e >> 1)) + 2 (e & 1) + (g >> 1), so rho >> 1 =
+          // 4 (mt & 1) + e and rho & 1 = g >> 1: [bit e] << (C + 16 (g >> 1)))
           constexpr uint32_t C = 8 * (n & 1) + 4 * (mt & 1);
           const uint32_t b = bits << (C + gsh);
           if constexpr ((mt & 3) == 0 && p == 0) mw[d] = b;
@@ -2044,9 +2150,18 @@ struct FwdWave16 {
     } else if constexpr (L == LFA) {  // the alpha row: row 0 = register 0 of lane group 0
       if constexpr (p == 0) alpha = acc[0];
     } else if constexpr (p == 0) {    // LRGB: rows 0..2 = registers 0..2 of lane group 0
-      rgb0 = acc[0];
-      rgb1 = acc[1];
-      rgb2 = acc[2];
+      if constexpr (F32) {
+        // rows f32w_row(4 g + e): 0 and 2 in registers 0, 1 of lane group 0, 1 in register 0 of lane group 2
+        static_assert(f32w_row(0) == 0 && f32w_row(8) == 1 && f32w_row(1) == 2, "the rgb rows of the wide fp32 unit");
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[0]), __float_as_uint(acc[0]), false, false);
+        rgb0 = acc[0];
+        rgb1 = __uint_as_float(r[1]);  // (lanes < 32: the value of lane + 32)
+        rgb2 = acc[1];
+      } else {
+        rgb0 = acc[0];
+        rgb1 = acc[1];
+        rgb2 = acc[2];
+      }
     }
   }
 
@@ -2054,11 +2169,11 @@ struct FwdWave16 {
     constexpr int NG = GT::t.n;
     if constexpr (gi + PF < NG && dma_spread<P>() == 0) fetch<gi + PF>();
     const uint32_t sl = lds_base + (uint32_t)((gi % NSLOT) * SLOT_CAP * 1024);
-    wbg = lds_ptr(sl + (uint32_t)(g * 16));
-    group_body<P, 2, DENSITY, gi>(*this, lds_ptr(sl + (uint32_t)(lane * 16)));
+    wbg = lds_ptr(sl + (F32 ? 16u * (uint32_t)(g & 1) + 4u * (uint32_t)(g >> 1) : 16u * (uint32_t)g));
+    group_body<P, DIR, DENSITY, gi>(*this, lds_ptr(sl + a_off));
     constexpr int N = dma_spread<P>() > 0
-        ? handoff_vmcnt_spread<P, 2, DENSITY>(gi, [](int u) constexpr { return unit_stores(u); })
-        : handoff_vmcnt<P, 2, DENSITY>(gi, [](int i) constexpr { return group_stores(i); }, STORE ? PRO_ST : 0);
+        ? handoff_vmcnt_spread<P, DIR, DENSITY>(gi, [](int u) constexpr { return unit_stores(u); })
+        : handoff_vmcnt<P, DIR, DENSITY>(gi, [](int i) constexpr { return group_stores(i); }, STORE ? PRO_ST : 0);
     if constexpr (gi + 1 < NG) wait_barrier<N>();
   }
 
@@ -2087,7 +2202,7 @@ struct FwdWave16 {
     {  // group 0 landed: younger = the DMAs of groups 1 .. PF - 1 and the PE stores (3 K-blocks x 2 halves)
       constexpr int N0 = [] {
         int n = STORE ? PRO_ST : 0;
-        for (int j = 1; j < PF && j < GT::t.n; ++j) n += group_dma<P, 2, DENSITY>(j);
+        for (int j = 1; j < PF && j < GT::t.n; ++j) n += group_dma<P, DIR, DENSITY>(j);
         return n;
       }();
       wait_barrier<N0>();
@@ -3307,20 +3422,19 @@ void mlp_fwd_train_impl(const FwdArgs& a, hipStream_t stream) {
 #define NERF_BF3_WIDE 1
 #endif
 using PBF3F = std::conditional_t<NERF_BF3_WIDE != 0, PBF3W, PBF3>;
-// The fp32 TRAINING forward: PF32's, or with -DNERF_F32_WIDE=1 the wide 16x16x4 kernel (PF32W, round 6; the
-// inference forwards -- renders, the march, the bake -- stay PF32 either way: another summation order moves the
-// few ill-conditioned CDF bins of the full-frame fixtures).  The fp32 forward pack then holds both
-// layouts, PF32's units first (nerf_mlp_packed_bytes), and the training forward reads the second.  Not the
-// default (profiles/r6/f32w_*.json): 4.9 % faster (4.863 -> 4.625 ms per 524,288 samples), deterministic, masks
-// equal to its activations' non-zeros, raw within 2.7e-7 of PF32's -- but its summation order flips the ReLU
-// branch of a few near-zero pre-activations that PF32's order and the reference's agree on, and the 4,096-ray
-// fine-net L0 bias gradient then sits 9.4e-4 (of the tensor's largest) from the reference's against the fp32
-// contract's 1e-4 (PF32: 5.5e-5; tests/test_gpu_trained.py::test_loss_gradients_fp32).
+// The fp32 TRAINING forward: the wide 16x16x4 kernel (PF32W) or, with -DNERF_F32_WIDE=0, PF32's 32x32x2 one; the
+// inference forwards -- renders, the march, the bake -- are PF32 either way.  Both read the one fp32 forward pack
+// (PF32's DIR 0 layout) and produce the same bits: the wide kernel feeds the matrix pipe PF32's K sequence
+// (struct PF32W; tests/test_gpu_f32_wide_forward.py compares raw, activations and masks bitwise), so the fp32
+// gradient contract and the full-frame fixtures hold for it by construction.  (Round 6's wide forward summed in
+// its own order, k16_feat: 4.9 % faster than PF32's, but the order flipped the ReLU branch of 5.6e-7 of the
+// pre-activations and moved the 4,096-ray fine-net L0 bias gradient 9.4e-4 from the reference's against the
+// contract's 1e-4 -- it was never the default and is gone.)  nerf_mlp_fwd's flags bit 2 runs PF32's training
+// forward whatever the default: the reference of the bitwise test and the A/B arm of tools/mlp_bench.py.
 #ifndef NERF_F32_WIDE
-#define NERF_F32_WIDE 0
+#define NERF_F32_WIDE 1
 #endif
 using PF32T = std::conditional_t<NERF_F32_WIDE != 0, PF32W, PF32>;
-[[maybe_unused]] constexpr int64_t F32W_PACK_OFF = NERF_F32_WIDE ? total_chunks(PF32::CH, 0) * 1024 : 0;
 // The dX of fp32 and bf16x3: the wide 16x16 kernels (DxWave16 over 16-row units, round 6) or, with
 // -DNERF_F32_WIDE_DX=0 / -DNERF_BF3_WIDE_DX=0, the 32x32 ones; their W^T packs follow (bwd_layout).  The dZ they
 // store is the same old-layout tile-block list either way (the dW is unchanged).
@@ -3417,13 +3531,11 @@ NERF_MLP_I_PACK(, PBF6)
 #else
 #define NERF_PP_FWD NERF_PP
 #endif
-#if NERF_MLP_PREC == 0
-#define NERF_PP_FWDT PF32T  // (the fp32 training forward: PF32W unless NERF_F32_WIDE=0)
-#else
-#define NERF_PP_FWDT NERF_PP_FWD
-#endif
 #if !defined(NERF_MLP_PART) || NERF_MLP_PART == 0
-NERF_MLP_I_FWDT(, NERF_PP_FWDT)
+NERF_MLP_I_FWDT(, NERF_PP_FWD)
+#endif
+#if NERF_MLP_PREC == 0 && (!defined(NERF_MLP_PART) || NERF_MLP_PART == 4)
+NERF_MLP_I_FWDT(, PF32W)  // (the wide fp32 training forward, a translation unit of its own)
 #endif
 #if !defined(NERF_MLP_PART) || NERF_MLP_PART == 1
 NERF_MLP_I_FWDI(, NERF_PP_FWD)
@@ -3449,8 +3561,8 @@ NERF_MLP_I_PACK(, NERF_PP)
 #if NERF_MLP_PREC == 2 && (NERF_BF3_WIDE || NERF_BF3_WIDE_DX)
 NERF_MLP_I_PACK(, PBF3W)
 #endif
-#if NERF_MLP_PREC == 0 && (NERF_F32_WIDE || NERF_F32_WIDE_DX)
-NERF_MLP_I_PACK(, PF32W)
+#if NERF_MLP_PREC == 0 && NERF_F32_WIDE_DX
+NERF_MLP_I_PACK(, PF32W)  // (the W^T pack of the wide dX; the wide forward reads PF32's forward pack)
 #endif
 #if NERF_MLP_PREC == 1 && NERF_BF16_WIDE_DX
 NERF_MLP_I_PACK(, PBF16W)
@@ -3483,8 +3595,6 @@ int64_t nerf_mlp_packed_bytes(int dtype, int dir) {
   if (!train_dtype(dtype) || (dir != 0 && dir != 1)) return -1;
   const int p = dir == 0 ? fwd_prec(dtype) : bwd_prec(dtype);
   if (p == 2 && dir == 0) return total_chunks(PBF3F::CH, fwd_layout<PBF3F>()) * 1024;  // (the wide bf16x3 forward)
-  if (p == 0 && dir == 0 && NERF_F32_WIDE)  // PF32's units, then PF32W's (the training forward)
-    return F32W_PACK_OFF + total_chunks(PF32W::CH, fwd_layout<PF32W>()) * 1024;
   if (p == 0 && dir == 1) return total_chunks(PF32X::CH, bwd_layout<PF32X>()) * 1024;  // (the fp32 dX)
   if (p == 2 && dir == 1) return total_chunks(PBF3X::CH, bwd_layout<PBF3X>()) * 1024;  // (the bf16x3 dX)
   if (p == 1 && dir == 1) return total_chunks(PBF16X::CH, bwd_layout<PBF16X>()) * 1024;  // (the bf16 dX)
@@ -3518,10 +3628,7 @@ int nerf_mlp_pack(const float* const* params, int dtype, void* packed_fwd, void*
     const int p = dir == 0 ? fwd_prec(dtype) : bwd_prec(dtype);
     if (p == 4) mlp_pack_impl<PBF6>(prm, dir, (char*)dst, stream);
     else if (p == 0 && dir == 1) mlp_pack_impl<PF32X>(prm, dir, (char*)dst, stream);
-    else if (p == 0) {
-      mlp_pack_impl<PF32>(prm, dir, (char*)dst, stream);
-      if (dir == 0 && NERF_F32_WIDE) mlp_pack_impl<PF32T>(prm, dir, (char*)dst + F32W_PACK_OFF, stream);
-    }
+    else if (p == 0) mlp_pack_impl<PF32>(prm, dir, (char*)dst, stream);  // (every fp32 forward, PF32W's too)
     else if (p == 1 && dir == 1) mlp_pack_impl<PBF16X>(prm, dir, (char*)dst, stream);
     else if (p == 1) mlp_pack_impl<PBF16>(prm, dir, (char*)dst, stream);
     else if (dir == 0) mlp_pack_impl<PBF3F>(prm, dir, (char*)dst, stream);
@@ -3531,7 +3638,8 @@ int nerf_mlp_pack(const float* const* params, int dtype, void* packed_fwd, void*
   return 0;
 }
 
-// flags: bit0 = store activations + masks for backward, bit1 = density only
+// flags: bit0 = store activations + masks for backward, bit1 = density only, bit2 (dtype 0 with bit0 only) = the
+// 32x32 PF32 training forward instead of the default one (the same pack, the same bits)
 int nerf_mlp_fwd(const void* packed_fwd, int dtype, const float* pts, const float* viewdirs, int samples_per_dir,
                  const int32_t* dir_index, int64_t M, int flags, float* raw, void* act, uint16_t* masks,
                  hipStream_t stream) {
@@ -3539,7 +3647,10 @@ int nerf_mlp_fwd(const void* packed_fwd, int dtype, const float* pts, const floa
   NERF_REQUIRE(dtype != 4 || flags == 0, "nerf_mlp_fwd: dtype 4 (bf16x6) is an inference forward only (flags 0)");
   NERF_REQUIRE(M >= 0, "nerf_mlp_fwd: M < 0");
   if (M == 0) return 0;
-  const bool store = flags & 1, density = flags & 2;
+  const bool store = flags & 1, density = flags & 2, narrow = flags & 4;
+  NERF_REQUIRE(!narrow || (dtype == 0 && store),
+               "nerf_mlp_fwd: flags bit 2 (the 32x32 fp32 training forward) needs dtype 0 and bit 0, got dtype %d flags 0x%x",
+               dtype, flags);
   NERF_REQUIRE(packed_fwd && pts && raw, "nerf_mlp_fwd: null pointer");
   NERF_REQUIRE(density || viewdirs, "nerf_mlp_fwd: viewdirs required unless density-only");
   NERF_REQUIRE(density || dir_index || samples_per_dir > 0, "nerf_mlp_fwd: samples_per_dir must be > 0");
@@ -3548,10 +3659,8 @@ int nerf_mlp_fwd(const void* packed_fwd, int dtype, const float* pts, const floa
   FwdArgs a{(const char*)packed_fwd, pts, viewdirs, dir_index, samples_per_dir, M,
             nerf_mlp_padded_samples(M) / 32, raw, act, masks};
   if (store) {
-    if (dtype == 0) {
-      a.wpack += F32W_PACK_OFF;  // (the PF32W units of the fp32 pack)
-      mlp_fwd_train_impl<PF32T>(a, stream);
-    }
+    if (dtype == 0 && narrow) mlp_fwd_train_impl<PF32>(a, stream);
+    else if (dtype == 0) mlp_fwd_train_impl<PF32T>(a, stream);
     else if (dtype == 1) mlp_fwd_train_impl<PBF16>(a, stream);
     else if (dtype == 2) mlp_fwd_train_impl<PBF3F>(a, stream);
     else mlp_fwd_train_half_impl(a, stream);
@@ -3777,8 +3886,8 @@ NERF_PINNED(NERF_DW_COST_TABLE_BF, 1)
 #endif
 #if defined(NERF_BF3_WIDE)
 static_assert(NERF_BF3_WIDE == 0 || NERF_BF3_WIDE == 1, "NERF_BF3_WIDE: 0 (32x32 bf16x3 forward) or 1 (wide)");
-// (the other kernel selectors: NERF_F32_WIDE -- the wide fp32 training forward, opt-in, off the fp32 gradient
-// contract; NERF_F32_WIDE_DX / NERF_BF3_WIDE_DX -- the wide dX, on; NERF_BF16_WIDE_DX -- the wide bf16 dX, opt-in,
+// (the other kernel selectors: NERF_F32_WIDE -- the wide fp32 training forward, on, bit-identical to PF32's;
+// NERF_F32_WIDE_DX / NERF_BF3_WIDE_DX -- the wide dX, on; NERF_BF16_WIDE_DX -- the wide bf16 dX, opt-in,
 // slower; each 0 or 1, every one of the kernels they select compiles under FinishSchedule and tools/asm_check.py)
 static_assert((NERF_F32_WIDE == 0 || NERF_F32_WIDE == 1) && (NERF_F32_WIDE_DX == 0 || NERF_F32_WIDE_DX == 1) &&
                   (NERF_BF3_WIDE_DX == 0 || NERF_BF3_WIDE_DX == 1) && (NERF_BF16_WIDE_DX == 0 || NERF_BF16_WIDE_DX == 1),

@@ -163,6 +163,46 @@ __host__ __device__ constexpr int fwd16_out_row0(int L, int m) { return (L == LF
 __host__ __device__ constexpr int fwd16_out_valid(int L, int m) {
   return (L == LFA && m == 16) ? 1 : L == LRGB ? 3 : 16;
 }
+// The wide fp32 forward (PF32W, v_mfma_f32_16x16x4_f32) in PF32's summation order.  The 32x32x2 kernel
+// consumes a 32-feature input tile as 16 MFMAs rho = 0..15, each taking feature acc_row(rho, 0) then
+// acc_row(rho, 1): position p = 2 rho + h of the tile's K sequence.  A 16x16x4 MFMA sums its four lane groups
+// g = lane >> 4 in order, so MFMA j of a K-block covers positions 4 j + g: register j of lane group g holds
+__host__ __device__ constexpr int f32w_feat(int g, int j) { return acc_row(2 * j + (g >> 1), g & 1); }
+static_assert(f32w_feat(0, 0) == 0 && f32w_feat(1, 0) == 4 && f32w_feat(2, 0) == 1 && f32w_feat(3, 7) == 31, "f32w_feat");
+// A 16x16 accumulator leaves row 4 g + e of 16-row unit mt in register e of lane group g, which IS register
+// 4 (mt & 1) + e of the next layer's K-block mt >> 1: A-row a of the unit carries output feature 16 mt + f32w_row(a)
+__host__ __device__ constexpr int f32w_row(int a) { return f32w_feat(a >> 2, a & 3); }
+// the weight column (of the layer's fwd_out_weight) that MFMA j of K-block t of layer L multiplies in lane group
+// g, -1 on a padding feature (tests/test_f32_wide_order_cpu.py prints this table)
+__host__ __device__ constexpr int f32w_fwd_column(int L, int t, int j, int g) {
+  return f32w_feat(g, j) < fwd_in_valid(L, t) ? fwd_in_colbase(L, t) + f32w_feat(g, j) : -1;
+}
+// ... which walks PF32's (tile, rho, h) sequence exactly, in every layer, and whose output rows land on the
+// registers the next layer reads them from
+__host__ __device__ constexpr bool f32w_order_ok() {
+  for (int L = 0; L < NLAYER; ++L)
+    for (int t = 0; t < fwd_in_tiles(L); ++t)
+      for (int rho = 0; rho < 16; ++rho)
+        for (int h = 0; h < 2; ++h) {
+          const int p = 2 * rho + h, j = p >> 2, g = p & 3;
+          const int col = acc_row(rho, h) < fwd_in_valid(L, t) ? fwd_in_colbase(L, t) + acc_row(rho, h) : -1;
+          if (f32w_fwd_column(L, t, j, g) != col) return false;
+        }
+  for (int mt = 0; mt < 2; ++mt)
+    for (int g = 0; g < 4; ++g)
+      for (int e = 0; e < 4; ++e)
+        if (16 * mt + f32w_row(4 * g + e) != f32w_feat(g, 4 * mt + e)) return false;
+  bool seen[16] = {};
+  for (int a = 0; a < 16; ++a) {
+    seen[f32w_row(a)] = true;  // (a permutation of the unit's 16 rows; the kernel computes it from the lane's bits)
+    if (f32w_row(a) != 8 * ((a >> 1) & 1) + 4 * ((a >> 2) & 1) + 2 * (a & 1) + (a >> 3)) return false;
+  }
+  for (int r = 0; r < 16; ++r)
+    if (!seen[r]) return false;
+  return true;
+}
+static_assert(f32w_order_ok(), "the wide fp32 forward's K order is not PF32's");
+
 // 16-row dX units (round 6: the wide dX of PF32W / PBF3W): unit = one 16-row half m & 1 of output tile m >> 1 of a
 // dX stage; its input is the stage's list of 32-feature K-blocks, in the same permuted order (k16_feat)
 __host__ __device__ constexpr int bwd16_out_tiles(int s) { return 2 * bwd_out_tiles(s); }

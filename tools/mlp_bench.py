@@ -38,9 +38,15 @@ def main():
                     help="with --chunks: the training step's backward (the M-sample fine net in chunks, then an "
                          "N-sample coarse net) with every dW on a second stream, so that the next dX overlaps it; "
                          "N = this value")
+    ap.add_argument("--f32-ab", default=None, metavar="M[,M...]",
+                    help="the fp32 training forward, default (wide 16x16x4) against flags bit 2 (32x32x2, "
+                         "NERF_MLP_F32_NARROW), interleaved in this process at each sample count: per-round ms of both "
+                         "arms, medians, the spread between repeats of one arm, and whether the outputs are bit-equal")
     args = ap.parse_args()
     if args.lib:
         _lib.LIB_PATH = os.path.abspath(args.lib)
+    if args.f32_ab:
+        return f32_ab(args)
     if args.libs:
         return compare(args)
     dev = torch.device("cuda:0")
@@ -210,6 +216,61 @@ def overlapped_backward(args, L, dt, M, pb, d_raw, masks, act, dz, grad):
             out["ms"][key] = round(times[len(times) // 2], 4)
         g_s, g_o = grads[f"{C}_seq"], grads[f"{C}_overlap"]
         out[f"{C}_bit_equal"] = bool(torch.equal(g_s[0], g_o[0]) and torch.equal(g_s[1], g_o[1]))
+    print(json.dumps(out), flush=True)
+
+
+def f32_ab(args):
+    """One process, one library, one forward pack: nerf_mlp_fwd(dtype 0, flags 1) against flags 1 | 4, A B A B ...
+    per round.  `spread` of an arm = (max - min) / median of its rounds; `gain` = 1 - wide / narrow (medians); the
+    adoption rule asks gain >= 10 x the larger spread."""
+    import statistics
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    shapes = [(256, 63), (256,)] + [(256, 256), (256,)] * 4 + [(256, 319), (256,)] + [(256, 256), (256,)] * 2 + \
+             [(128, 283), (128,), (256, 256), (256,), (1, 256), (1,), (3, 128), (3,)]
+    params = [(torch.rand(s, device=dev) - 0.5) * (0.2 if len(s) == 2 else 0.1) for s in shapes]
+    packer = ops.PackedMLP(params)
+    L = lib()
+    pf = packer.get(0, 0)
+    out = {"rounds": args.rounds, "reps": args.reps, "arms": {"wide": "flags 1", "narrow": "flags 1 | 4"}, "M": {}}
+    for M in [int(m) for m in args.f32_ab.split(",")]:
+        pts = (torch.rand(M, 3, device=dev) - 0.5) * 3
+        vd = torch.nn.functional.normalize(torch.randn(M // 192 + 1, 3, device=dev), dim=-1)
+        s = stream_of(pts)
+        bufs = {arm: dict(raw=torch.zeros(M, 4, device=dev),
+                          act=torch.zeros(L.nerf_mlp_act_bytes(0, M), dtype=torch.uint8, device=dev),
+                          masks=torch.zeros(L.nerf_mlp_mask_bytes(M), dtype=torch.uint8, device=dev))
+                for arm in ("wide", "narrow")}
+
+        def run(arm):
+            b = bufs[arm]
+            check(L.nerf_mlp_fwd(ptr(pf), 0, ptr(pts), ptr(vd), 192, None, M, 1 if arm == "wide" else 5, ptr(b["raw"]),
+                                 ptr(b["act"]), ptr(b["masks"]), s), arm)
+        times = {"wide": [], "narrow": []}
+        for r in range(args.rounds + 1):
+            for arm in ("wide", "narrow"):
+                run(arm)
+                torch.cuda.synchronize()
+                a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(args.reps):
+                    run(arm)
+                e.record()
+                torch.cuda.synchronize()
+                if r:
+                    times[arm].append(a.elapsed_time(e) / args.reps)
+        med = {arm: statistics.median(t) for arm, t in times.items()}
+        spread = {arm: (max(t) - min(t)) / med[arm] for arm, t in times.items()}
+        gain = 1.0 - med["wide"] / med["narrow"]
+        out["M"][str(M)] = {
+            "ms_rounds": {arm: [round(x, 4) for x in t] for arm, t in times.items()},
+            "ms": {arm: round(v, 4) for arm, v in med.items()},
+            "tflops": {arm: round(FLOP["fwd_train"] * M / (v * 1e-3) / 1e12, 1) for arm, v in med.items()},
+            "spread": {arm: round(v, 5) for arm, v in spread.items()},
+            "gain": round(gain, 5),
+            "gain_over_10x_spread": bool(gain >= 10 * max(spread.values())),
+            "bit_equal": {k: bool(torch.equal(bufs["wide"][k], bufs["narrow"][k])) for k in ("raw", "act", "masks")},
+        }
     print(json.dumps(out), flush=True)
 
 
