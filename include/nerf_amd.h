@@ -269,6 +269,43 @@ int nerf_march_seg_composite_bwd(const float* raw, const float* rays, int64_t N,
                                  const float* g_rgb, const float* g_depth, const float* g_acc, float* g_raw,
                                  hipStream_t stream);
 
+/* ---- (a12) jittered march steps (training) -----------------------------------------------------------
+ * A per-ray shift of the steps' depths: t(r, k) = t_table[k] + t_shift[r], one separately rounded fp32
+ * add, so a ray shifted by c marches the table t_table + c bit for bit; the empty-space skip compares
+ * the shifted depths and stays exact.  t_shift is [N] fp32 on the device, or null: the table as it is,
+ * with no add (what the entry points without the argument pass).  The same array goes to every call of
+ * one march (gather, composite, segments, seg_composite_fwd / _bwd).
+ *
+ * nerf_march_jitter: t_shift[r] = u(r) * step_size, u the Philox-4x32-10 uniform of counter
+ * (r lo, r hi, offset lo, offset hi) and key (seed lo, seed hi), first word, (x >> 8) * 2^-24 -- the
+ * stratified sampler's stream.  Values lie in [0, step_size).  N == 0 is a no-op; N < 0 or a null
+ * t_shift with N > 0 is -22 before any launch.  No atomics, workspace, allocation or host sync. */
+int nerf_march_jitter(int64_t N, float step_size, uint64_t seed, uint64_t offset, float* t_shift, hipStream_t stream);
+int nerf_march_gather_shift(const float* rays, int64_t N, const float* t_table, int n_steps, const uint8_t* grid,
+                            int res, const uint8_t* macro, const float* bbox_host, int K, int k_low, float t_split,
+                            float* T, float* rgb, float* depth, float* acc, int32_t* next_step, uint8_t* alive,
+                            uint8_t* exhausted, int32_t* counters, unsigned long long* evaluated,
+                            int32_t* start_step_scratch, int32_t* out_ray, int32_t* out_step, float* out_pts,
+                            int32_t* ray_off, int32_t* ray_cnt, int64_t cap, const float* t_shift,
+                            hipStream_t stream);
+int nerf_march_composite_shift(const float* raw, const float* rays, int64_t N, const float* t_table,
+                               const int32_t* ray_off, const int32_t* ray_cnt, const int32_t* out_step, float* T,
+                               float* rgb, float* depth, float* acc, int32_t* next_step, uint8_t* alive,
+                               uint8_t* exhausted, float step_size, float t_thresh, unsigned long long* consumed,
+                               int32_t* ray_used, const float* t_shift, hipStream_t stream);
+int nerf_march_segments_shift(const float* rays, int64_t N, const float* t_table, int n_steps, const uint8_t* grid,
+                              int res, const uint8_t* macro, const float* bbox_host, const int32_t* seg_off,
+                              int32_t* out_ray, int32_t* out_step, float* out_pts, const float* t_shift,
+                              hipStream_t stream);
+int nerf_march_seg_composite_fwd_shift(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                       const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                       float* rgb, float* depth, float* acc, const float* t_shift,
+                                       hipStream_t stream);
+int nerf_march_seg_composite_bwd_shift(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                       const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                       const float* g_rgb, const float* g_depth, const float* g_acc, float* g_raw,
+                                       const float* t_shift, hipStream_t stream);
+
 /* ---- (a12) point budget: pass A's counts -> pass B's segments, cut at a budget of points ---------------
  * ray_used[N] (int32, >= 0) -> seg_off[N+1] (int32) and keep[2] (int64, device):
  * P[r] = sum_{q<r} ray_used[q] in 64-bit;  n_keep = the largest r in [0, N] with P[r] <= budget;

@@ -155,7 +155,29 @@ struct MarchGatherArgs {
   int32_t* ray_off;    // [N]
   int32_t* ray_cnt;    // [N]
   int64_t cap;
+  const float* t_shift;  // [N] per-ray shift of the march steps (nerf_march_jitter), or null: the table as it is
 };
+
+// A ray's depth at step s: t_table[s], plus the ray's shift when there is one -- a separately
+// rounded add, so a ray shifted by c marches the table t_table + c (rounded entry by entry)
+// bit for bit.  Without a shift array there is no add at all.  Every read of the table in the
+// march goes through this.  SHIFT is a template parameter of the march's kernels (the launches
+// pick the instantiation by t_shift != null), not a test inside the walk: the unshifted kernels
+// are the code they were before the shift existed.
+template <bool SHIFT>
+struct RayT {
+  const float* table;
+  float shift;
+  __device__ __forceinline__ float operator()(int s) const {
+    if constexpr (SHIFT) return fadd(table[s], shift);
+    else return table[s];
+  }
+};
+template <bool SHIFT>
+__device__ __forceinline__ RayT<SHIFT> ray_t(const float* t_table, const float* t_shift, int64_t r) {
+  if constexpr (SHIFT) return RayT<SHIFT>{t_table, t_shift[r]};
+  else return RayT<SHIFT>{t_table, 0.f};
+}
 
 __device__ __forceinline__ bool march_occupied(const MarchGatherArgs& a, const float* ray, float t, float* p,
                                                int* cell) {
@@ -174,8 +196,11 @@ __device__ __forceinline__ bool march_occupied(const MarchGatherArgs& a, const f
 // boundary cells that also hold the clamped outside -- and the computed p = o + t d is monotone
 // in t.  Every step whose t is below the first exit of the interval SHRUNK by a margin m is
 // therefore in the same empty cell, and is skipped; the walk resumes one step at a time near the
-// boundary.  m = max(1e-3 w, 2^-18 (|o| + t_abs |d| + |mn| + |mx|)), t_abs = max(8, |t| over the
-// table) (a far bound past 8 widens the margin with the coordinates): 1e-3 w is ~2.4e-5 at res 128, but
+// boundary.  With a per-ray shift (RayT) the steps' depths are fadd(t_table[j], shift): adding a
+// constant is monotone in fp32 too, so the shifted depths are still non-decreasing in j and every
+// comparison below is made on them, never on the bare table.  m = max(1e-3 w, 2^-18 (|o| +
+// t_abs |d| + |mn| + |mx|)), t_abs = max(8, |t| over the shifted table, i.e. at its ends) (a far
+// bound past 8 widens the margin with the coordinates): 1e-3 w is ~2.4e-5 at res 128, but
 // shrinks as 1/res (2.9e-6 at res 1024), while the fp32 errors of p = o + t d, of the interval
 // bounds and of t_exit d are a few ulps of the coordinates' magnitude (~1e-6 for |o| ~ 4, t <= 6
 // here): the absolute floor keeps the margin >= 8 such ulps at any resolution.  Returns the next
@@ -186,11 +211,12 @@ __device__ __forceinline__ bool march_occupied(const MarchGatherArgs& a, const f
 // same monotone argument over a union of cells -- so a ray crosses empty space ~8x faster (the
 // walk is a chain of dependent lookups: its length, not the lookups, sets a round's gather time).
 constexpr int MACRO = 8;
-__device__ __forceinline__ int march_skip_empty(const MarchGatherArgs& a, const float* ray, int s, const int* cell,
-                                                int span) {
+template <class TR>
+__device__ __forceinline__ int march_skip_empty(const MarchGatherArgs& a, const TR& tr, const float* ray, int s,
+                                                const int* cell, int span) {
   // fp32 with approximate reciprocals: the errors (~1e-6 in p) are far inside the margin.
   // |t| is bounded by the table's ends (it is monotone); 8 is the floor the bound was tested at
-  const float t_abs = fmaxf(8.0f, fmaxf(fabsf(a.t_table[0]), fabsf(a.t_table[a.n_steps - 1])));
+  const float t_abs = fmaxf(8.0f, fmaxf(fabsf(tr(0)), fabsf(tr(a.n_steps - 1))));
   float t_exit = 3.0e38f;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -206,37 +232,40 @@ __device__ __forceinline__ int march_skip_empty(const MarchGatherArgs& a, const 
       t_exit = fminf(t_exit, (mn + (float)lo * w + m - ray[k]) * rd);
     }
   }
-  // last step j > s with t_table[j] < t_exit (steps are ~uniform: estimate, then correct)
-  const float t0 = a.t_table[s], t1 = a.t_table[a.n_steps > s + 1 ? s + 1 : s];
+  // last step j > s with t(j) < t_exit (steps are ~uniform: estimate, then correct)
+  const float t0 = tr(s), t1 = tr(a.n_steps > s + 1 ? s + 1 : s);
   int j = s;
   if (t1 > t0 && t_exit > t1) {
     const float est = (t_exit - t0) * __builtin_amdgcn_rcpf(t1 - t0);
     j = s + (int)fminf(est, (float)(a.n_steps - 1 - s)) - 1;
     if (j < s) j = s;
-    while (j + 1 < a.n_steps && a.t_table[j + 1] < t_exit) ++j;
-    while (j > s && a.t_table[j] >= t_exit) --j;
+    while (j + 1 < a.n_steps && tr(j + 1) < t_exit) ++j;
+    while (j > s && tr(j) >= t_exit) --j;
   }
   return j + 1;
 }
 
 // the step after an empty cell: the macro block's exit when the block is empty, else the cell's
-__device__ __forceinline__ int march_next_after_empty(const MarchGatherArgs& a, const float* ray, int s,
-                                                      const int* cell) {
+template <class TR>
+__device__ __forceinline__ int march_next_after_empty(const MarchGatherArgs& a, const TR& tr, const float* ray,
+                                                      int s, const int* cell) {
   int span = 1;
   if (a.macro) {
     const int mres = (a.res + MACRO - 1) / MACRO;
     const int64_t j = ((int64_t)(cell[0] / MACRO) * mres + cell[1] / MACRO) * mres + cell[2] / MACRO;
     if (a.macro[j] == 0) span = MACRO;
   }
-  return march_skip_empty(a, ray, s, cell, span);
+  return march_skip_empty(a, tr, ray, s, cell, span);
 }
 
+template <bool SHIFT>
 __global__ void march_gather_kernel(MarchGatherArgs a) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = r < a.N;
   const bool live = in && a.st.alive[r];
   int cnt = 0, s = live ? a.st.next_step[r] : 0;
   const float* ray = a.rays + (in ? r : 0) * 6;
+  const RayT<SHIFT> tr = ray_t<SHIFT>(a.t_table, a.t_shift, in ? r : 0);
   float p[3];
   if (live) {
     // a ray whose transmittance has already dropped is near its termination step: gathering
@@ -245,11 +274,11 @@ __global__ void march_gather_kernel(MarchGatherArgs a) {
     const int k = a.st.T[r] < a.t_split ? (a.k_low < a.K ? a.k_low : a.K) : a.K;
     int cell[3];
     while (s < a.n_steps && cnt < k) {
-      if (march_occupied(a, ray, a.t_table[s], p, cell)) {
+      if (march_occupied(a, ray, tr(s), p, cell)) {
         ++cnt;
         ++s;
       } else {
-        s = march_next_after_empty(a, ray, s, cell);
+        s = march_next_after_empty(a, tr, ray, s, cell);
       }
     }
   }
@@ -301,6 +330,7 @@ struct MarchEmitArgs {
   const int32_t* start_step;  // [N] step before the gather
 };
 
+template <bool SHIFT>
 __global__ void march_emit_kernel(MarchEmitArgs e) {
   const MarchGatherArgs& a = e.g;
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -309,12 +339,13 @@ __global__ void march_emit_kernel(MarchEmitArgs e) {
   const int cnt = c < 0 ? -c : c;  // (< 0: an overflowing ray's points below cap, written only)
   if (cnt == 0) return;
   const float* ray = a.rays + r * 6;
+  const RayT<SHIFT> tr = ray_t<SHIFT>(a.t_table, a.t_shift, r);
   int pos = a.ray_off[r];
   int k = 0;
   float p[3];
   int cell[3];
   for (int s = e.start_step[r]; k < cnt;) {  // the gather's walk, skips included
-    if (march_occupied(a, ray, a.t_table[s], p, cell)) {
+    if (march_occupied(a, ray, tr(s), p, cell)) {
       a.out_ray[pos + k] = (int32_t)r;
       a.out_step[pos + k] = s;
       a.out_pts[(int64_t)(pos + k) * 3 + 0] = p[0];
@@ -323,7 +354,7 @@ __global__ void march_emit_kernel(MarchEmitArgs e) {
       ++k;
       ++s;
     } else {
-      s = march_next_after_empty(a, ray, s, cell);
+      s = march_next_after_empty(a, tr, ray, s, cell);
     }
   }
 }
@@ -339,10 +370,13 @@ __global__ void march_emit_kernel(MarchEmitArgs e) {
 // same steps).  Outputs, counters and overflow handling are those of gather + emit.
 constexpr int MARCH_RUNS = 16;
 constexpr int MARCH_WAVES = 4;  // 256-thread blocks
-__device__ __forceinline__ void march_put(const MarchGatherArgs& a, int64_t r, const float* ray, int64_t at, int s) {
+template <class TR>
+__device__ __forceinline__ void march_put(const MarchGatherArgs& a, const TR& tr, int64_t r, const float* ray,
+                                          int64_t at, int s) {
   float p[3];
+  const float t = tr(s);
 #pragma unroll
-  for (int k = 0; k < 3; ++k) p[k] = fadd(ray[k], fmul(a.t_table[s], ray[3 + k]));  // = march_occupied's p
+  for (int k = 0; k < 3; ++k) p[k] = fadd(ray[k], fmul(t, ray[3 + k]));  // = march_occupied's p
   a.out_ray[at] = (int32_t)r;
   a.out_step[at] = s;
   a.out_pts[at * 3 + 0] = p[0];
@@ -350,6 +384,7 @@ __device__ __forceinline__ void march_put(const MarchGatherArgs& a, int64_t r, c
   a.out_pts[at * 3 + 2] = p[2];
 }
 
+template <bool SHIFT>
 __global__ void __launch_bounds__(256) march_gather_emit_kernel(MarchGatherArgs a) {
   __shared__ uint32_t runs[MARCH_WAVES][MARCH_RUNS][64];  // (start << 16) | length, lane-minor
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -358,6 +393,7 @@ __global__ void __launch_bounds__(256) march_gather_emit_kernel(MarchGatherArgs 
   const bool live = in && a.st.alive[r];
   int cnt = 0, s = live ? a.st.next_step[r] : 0;
   const float* ray = a.rays + (in ? r : 0) * 6;
+  const RayT<SHIFT> tr = ray_t<SHIFT>(a.t_table, a.t_shift, in ? r : 0);
   int nrun = 0, cur_start = 0, cur_len = 0;  // recorded runs; the open run
   int ovf_step = -1;                           // first unrecorded run's step
   if (live) {
@@ -365,7 +401,7 @@ __global__ void __launch_bounds__(256) march_gather_emit_kernel(MarchGatherArgs 
     float p[3];
     int cell[3];
     while (s < a.n_steps && cnt < k) {
-      if (march_occupied(a, ray, a.t_table[s], p, cell)) {
+      if (march_occupied(a, ray, tr(s), p, cell)) {
         if (ovf_step < 0) {
           if (cur_len > 0 && s == cur_start + cur_len && cur_len < 0xFFFF) {
             ++cur_len;
@@ -387,7 +423,7 @@ __global__ void __launch_bounds__(256) march_gather_emit_kernel(MarchGatherArgs 
         ++cnt;
         ++s;
       } else {
-        s = march_next_after_empty(a, ray, s, cell);
+        s = march_next_after_empty(a, tr, ray, s, cell);
       }
     }
   }
@@ -431,20 +467,20 @@ __global__ void __launch_bounds__(256) march_gather_emit_kernel(MarchGatherArgs 
   for (int i = 0; i < nrun && kk < nwrite; ++i) {
     const uint32_t ru = runs[w][i][l];
     const int st = (int)(ru >> 16), ln = (int)(ru & 0xFFFF);
-    for (int j = 0; j < ln && kk < nwrite; ++j, ++kk) march_put(a, r, ray, (int64_t)pos + kk, st + j);
+    for (int j = 0; j < ln && kk < nwrite; ++j, ++kk) march_put(a, tr, r, ray, (int64_t)pos + kk, st + j);
   }
   if (ovf_step < 0) {
-    for (int j = 0; j < cur_len && kk < nwrite; ++j, ++kk) march_put(a, r, ray, (int64_t)pos + kk, cur_start + j);
+    for (int j = 0; j < cur_len && kk < nwrite; ++j, ++kk) march_put(a, tr, r, ray, (int64_t)pos + kk, cur_start + j);
   } else {
     float p[3];
     int cell[3];
     for (int ss = ovf_step; kk < nwrite;) {
-      if (march_occupied(a, ray, a.t_table[ss], p, cell)) {
-        march_put(a, r, ray, (int64_t)pos + kk, ss);
+      if (march_occupied(a, ray, tr(ss), p, cell)) {
+        march_put(a, tr, r, ray, (int64_t)pos + kk, ss);
         ++kk;
         ++ss;
       } else {
-        ss = march_next_after_empty(a, ray, ss, cell);
+        ss = march_next_after_empty(a, tr, ray, ss, cell);
       }
     }
   }
@@ -462,22 +498,26 @@ struct MarchCompArgs {
   float step_size, t_thresh;
   unsigned long long* consumed;  // += points composited (the reference's MLP queries) or null
   int32_t* ray_used;             // [N] += this ray's points composited this round, or null
+  const float* t_shift;          // [N] the gather's per-ray shift, or null
 };
 
+template <bool SHIFT>
 __device__ __forceinline__ int march_composite_ray_impl(const MarchCompArgs& a, int64_t r);
+template <bool SHIFT>
 __device__ __forceinline__ int march_composite_ray(const MarchCompArgs& a, int64_t r) {
-  return march_composite_ray_impl(a, r);
+  return march_composite_ray_impl<SHIFT>(a, r);
 }
 
 // Composites a ray's gathered points in step order and stops at T < t_thresh
 // (volume_renderer.py:327-341).  Points gathered past that step were evaluated speculatively
 // and are dropped; the points composited are exactly the reference's queries (:324), counted
 // into `consumed`.
+template <bool SHIFT>
 __global__ void march_composite_kernel(MarchCompArgs a) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = r < a.N && a.st.alive[r];
   int used = 0;
-  if (live) used = march_composite_ray(a, r);
+  if (live) used = march_composite_ray<SHIFT>(a, r);
   if (a.ray_used && live) a.ray_used[r] += used;
   if (a.consumed) {
     // wave-aggregated count
@@ -488,10 +528,12 @@ __global__ void march_composite_kernel(MarchCompArgs a) {
   }
 }
 
+template <bool SHIFT>
 __device__ __forceinline__ int march_composite_ray_impl(const MarchCompArgs& a, int64_t r) {
   const int c = a.ray_cnt[r], off = a.ray_off[r];
   const int cnt = c > 0 ? c : 0;  // (< 0: gathered nothing this round, see march_gather_kernel)
   const float* ray = a.rays + r * 6;
+  const RayT<SHIFT> tr = ray_t<SHIFT>(a.t_table, a.t_shift, r);
   const float dx = ray[3], dy = ray[4], dz = ray[5];
   const float dist = fmul(a.step_size, sqrtf(fadd(fadd(fmul(dx, dx), fmul(dy, dy)), fmul(dz, dz))));
   float T = a.st.T[r];
@@ -501,7 +543,7 @@ __device__ __forceinline__ int march_composite_ray_impl(const MarchCompArgs& a, 
   int used = cnt;
   for (int k = 0; k < cnt; ++k) {
     const float4 rw = *(const float4*)(a.raw + (int64_t)(off + k) * 4);
-    const float t = a.t_table[a.out_step[off + k]];
+    const float t = tr(a.out_step[off + k]);
     const float sr = 1.f / (1.f + expf(-rw.x)), sg = 1.f / (1.f + expf(-rw.y)), sb = 1.f / (1.f + expf(-rw.z));
     const float sigma = rw.w > 0.f ? rw.w : 0.f;
     const float alpha = fsub(1.f, expf(-fmul(sigma, dist)));
@@ -541,6 +583,17 @@ __global__ void march_macro_kernel(const uint8_t* grid, int res, uint8_t* macro)
   macro[b] = any ? 1 : 0;
 }
 
+// Jittered steps (training): one shift per ray, uniform in [0, step_size), from the Philox stream
+// the stratified sampler draws from (counter = ray, offset; key = seed).  u <= 1 - 2^-24, so the
+// rounded product stays below step_size and a shifted ray still samples inside [near, far).  Its
+// own launch: both passes of the differentiable march read the same array, and a test can
+// inject one.
+__global__ void march_jitter_kernel(int64_t N, float step_size, uint64_t seed, uint64_t offset, float* t_shift) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= N) return;
+  t_shift[r] = fmul(rng_uniform(seed, offset, (uint64_t)r), step_size);
+}
+
 struct MarchInitArgs { MarchState st; int64_t N; };
 __global__ void march_init_kernel(MarchInitArgs a) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -575,23 +628,25 @@ __global__ void march_finish_kernel(MarchFinishArgs a) {
 // One thread per ray: the gather's walk from step 0 (same skips, same points), the ray's first
 // seg_off[r+1] - seg_off[r] occupied steps written at seg_off[r].  A ray with fewer occupied
 // steps than its count gets step -1 and its origin in the surplus positions.
+template <bool SHIFT>
 __global__ void march_segments_kernel(MarchGatherArgs a, const int32_t* seg_off) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.N) return;
   const int64_t pos = seg_off[r];
   const int64_t cnt = (int64_t)seg_off[r + 1] - pos;
   const float* ray = a.rays + r * 6;
+  const RayT<SHIFT> tr = ray_t<SHIFT>(a.t_table, a.t_shift, r);
   int64_t k = 0;
   int s = 0;
   float p[3];
   int cell[3];
   while (s < a.n_steps && k < cnt) {
-    if (march_occupied(a, ray, a.t_table[s], p, cell)) {
-      march_put(a, r, ray, pos + k, s);
+    if (march_occupied(a, ray, tr(s), p, cell)) {
+      march_put(a, tr, r, ray, pos + k, s);
       ++k;
       ++s;
     } else {
-      s = march_next_after_empty(a, ray, s, cell);
+      s = march_next_after_empty(a, tr, ray, s, cell);
     }
   }
   for (; k < cnt; ++k) {
@@ -619,6 +674,7 @@ struct SegCompArgs {
   const float* g_depth;
   const float* g_acc;
   float* g_raw;  // [M,4]
+  const float* t_shift;  // [N] the walk's per-ray shift, or null
 };
 
 constexpr int SEG_WAVES = 4;  // rays (waves) per 256-thread block
@@ -661,12 +717,14 @@ __device__ __forceinline__ float seg_sigmoid(float x) { return 1.f / (1.f + expf
 // One wave per ray, lanes on consecutive points (raw read as coalesced float4), 64 points a chunk:
 // T_k = T_in * prod_{j<k in chunk} (1 - alpha_j) by a product scan across the lanes (in double, as
 // the compositor of render()), T_in carried from chunk to chunk; every point of the segment is used.
+template <bool SHIFT>
 __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompArgs a) {
   const int64_t r = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
   if (r >= a.N) return;  // (wave-uniform)
   const int l = lane_id();
   const int64_t beg = a.seg_off[r], end = a.seg_off[r + 1];
   const float dist = seg_dist(a, r);
+  const RayT<SHIFT> tr = ray_t<SHIFT>(a.t_table, a.t_shift, r);
   double Tin = 1.0, sr = 0.0, sg = 0.0, sb = 0.0, sd = 0.0, sa = 0.0;
   for (int64_t b = beg; b < end; b += 64) {
     const int64_t k = b + l;
@@ -681,7 +739,7 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompAr
       sr += w * (double)seg_sigmoid(rw.x);
       sg += w * (double)seg_sigmoid(rw.y);
       sb += w * (double)seg_sigmoid(rw.z);
-      sd += w * (double)a.t_table[st];
+      sd += w * (double)tr(st);
       sa += w;
     }
     Tin *= shfl_d(P, 63);
@@ -711,6 +769,7 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompAr
 // 4096 points: every ray of an 800-step march) and super-chunk j's (64 chunks each); a later
 // super-chunk's chunk entries are recomputed from its own entry when the reverse walk reaches it.
 // alpha_k = 1 (exp underflow) zeroes T from k + 1 on: every later gradient is exactly 0, no 0/0.
+template <bool SHIFT>
 __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_bwd_kernel(SegCompArgs a) {
   const int64_t r = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
   if (r >= a.N) return;  // (wave-uniform)
@@ -718,6 +777,7 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_bwd_kernel(SegCompAr
   const int64_t beg = a.seg_off[r], end = a.seg_off[r + 1];
   if (end <= beg) return;
   const float dist = seg_dist(a, r);
+  const RayT<SHIFT> tr = ray_t<SHIFT>(a.t_table, a.t_shift, r);
   const double gr = a.g_rgb ? (double)a.g_rgb[r * 3 + 0] : 0.0, gg = a.g_rgb ? (double)a.g_rgb[r * 3 + 1] : 0.0,
                gb = a.g_rgb ? (double)a.g_rgb[r * 3 + 2] : 0.0;
   const double gd = a.g_depth ? (double)a.g_depth[r] : 0.0;
@@ -765,7 +825,7 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_bwd_kernel(SegCompAr
         cx = seg_sigmoid(rw.x);
         cy = seg_sigmoid(rw.y);
         cz = seg_sigmoid(rw.z);
-        v = gr * (double)cx + gg * (double)cy + gb * (double)cz + gd * (double)a.t_table[st] + ga;
+        v = gr * (double)cx + gg * (double)cy + gb * (double)cz + gd * (double)tr(st) + ga;
       }
       // suffix composition: (A, B) of lane i = f_i o f_{i+1} o ... o f_63, f_j(x) = alpha_j v_j + (1 - alpha_j) x
       double A = (double)alpha * v, B = (double)om;
@@ -1069,23 +1129,35 @@ int nerf_march_macro(const uint8_t* grid, int res, uint8_t* macro, hipStream_t s
   return check_launch("nerf_march_macro");
 }
 
-int nerf_march_gather(const float* rays, int64_t N, const float* t_table, int n_steps, const uint8_t* grid, int res,
-                      const uint8_t* macro, const float* bbox_host, int K, int k_low, float t_split, float* T,
-                      float* rgb, float* depth,
-                      float* acc,
-                      int32_t* next_step, uint8_t* alive, uint8_t* exhausted, int32_t* counters,
-                      unsigned long long* evaluated, int32_t* start_step_scratch, int32_t* out_ray, int32_t* out_step,
-                      float* out_pts, int32_t* ray_off, int32_t* ray_cnt, int64_t cap, hipStream_t stream) {
+int nerf_march_jitter(int64_t N, float step_size, uint64_t seed, uint64_t offset, float* t_shift,
+                      hipStream_t stream) {
+  NERF_REQUIRE(N >= 0, "nerf_march_jitter: N must be >= 0, got %lld", (long long)N);
+  if (N == 0) return 0;
+  NERF_REQUIRE(t_shift, "nerf_march_jitter: t_shift is null");
+  hipLaunchKernelGGL(march_jitter_kernel, grid1(N), dim3(256), 0, stream, N, step_size, seed, offset, t_shift);
+  return check_launch("nerf_march_jitter");
+}
+
+// The *_shift entry points take the per-ray shift of the march steps (t_shift [N], or null: the
+// table as it is); the entry points without it forward a null shift.
+int nerf_march_gather_shift(const float* rays, int64_t N, const float* t_table, int n_steps, const uint8_t* grid,
+                            int res, const uint8_t* macro, const float* bbox_host, int K, int k_low, float t_split,
+                            float* T, float* rgb, float* depth, float* acc, int32_t* next_step, uint8_t* alive,
+                            uint8_t* exhausted, int32_t* counters, unsigned long long* evaluated,
+                            int32_t* start_step_scratch, int32_t* out_ray, int32_t* out_step, float* out_pts,
+                            int32_t* ray_off, int32_t* ray_cnt, int64_t cap, const float* t_shift,
+                            hipStream_t stream) {
   NERF_REQUIRE(N >= 0 && n_steps >= 0 && K > 0 && res > 1 && bbox_host, "nerf_march_gather: bad arguments");
   NERF_REQUIRE(cap >= K && cap <= INT32_MAX, "nerf_march_gather: need K <= cap <= INT32_MAX (point offsets are int32)");
   if (N == 0) return 0;
   NERF_REQUIRE(k_low > 0, "nerf_march_gather: k_low must be > 0");
   MarchGatherArgs a{rays, N, t_table, n_steps, grid, res, macro, make_bbox(bbox_host), K, k_low, t_split,
                     {T, rgb, depth, acc, next_step, alive, exhausted},
-                    counters, evaluated, out_ray, out_step, out_pts, ray_off, ray_cnt, cap};
+                    counters, evaluated, out_ray, out_step, out_pts, ray_off, ray_cnt, cap, t_shift};
   if (!start_step_scratch) {  // one pass: gather + emit fused (march_gather_emit_kernel)
     NERF_REQUIRE(n_steps < 65536, "nerf_march_gather: the one-pass form needs n_steps < 65536 (16-bit run starts)");
-    hipLaunchKernelGGL(march_gather_emit_kernel, grid1(N), dim3(256), 0, stream, a);
+    if (t_shift) hipLaunchKernelGGL(march_gather_emit_kernel<true>, grid1(N), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(march_gather_emit_kernel<false>, grid1(N), dim3(256), 0, stream, a);
     return check_launch("nerf_march_gather");
   }
   if (hipMemcpyAsync(start_step_scratch, next_step, N * sizeof(int32_t), hipMemcpyDeviceToDevice, stream) !=
@@ -1093,11 +1165,38 @@ int nerf_march_gather(const float* rays, int64_t N, const float* t_table, int n_
     set_error("nerf_march_gather: hipMemcpyAsync failed");
     return -5;
   }
-  hipLaunchKernelGGL(march_gather_kernel, grid1(N), dim3(256), 0, stream, a);
+  if (t_shift) hipLaunchKernelGGL(march_gather_kernel<true>, grid1(N), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(march_gather_kernel<false>, grid1(N), dim3(256), 0, stream, a);
   if (int e = check_launch("nerf_march_gather")) return e;
   MarchEmitArgs em{a, start_step_scratch};
-  hipLaunchKernelGGL(march_emit_kernel, grid1(N), dim3(256), 0, stream, em);
+  if (t_shift) hipLaunchKernelGGL(march_emit_kernel<true>, grid1(N), dim3(256), 0, stream, em);
+  else hipLaunchKernelGGL(march_emit_kernel<false>, grid1(N), dim3(256), 0, stream, em);
   return check_launch("nerf_march_emit");
+}
+
+int nerf_march_gather(const float* rays, int64_t N, const float* t_table, int n_steps, const uint8_t* grid, int res,
+                      const uint8_t* macro, const float* bbox_host, int K, int k_low, float t_split, float* T,
+                      float* rgb, float* depth,
+                      float* acc,
+                      int32_t* next_step, uint8_t* alive, uint8_t* exhausted, int32_t* counters,
+                      unsigned long long* evaluated, int32_t* start_step_scratch, int32_t* out_ray, int32_t* out_step,
+                      float* out_pts, int32_t* ray_off, int32_t* ray_cnt, int64_t cap, hipStream_t stream) {
+  return nerf_march_gather_shift(rays, N, t_table, n_steps, grid, res, macro, bbox_host, K, k_low, t_split, T, rgb,
+                                 depth, acc, next_step, alive, exhausted, counters, evaluated, start_step_scratch,
+                                 out_ray, out_step, out_pts, ray_off, ray_cnt, cap, nullptr, stream);
+}
+
+int nerf_march_composite_shift(const float* raw, const float* rays, int64_t N, const float* t_table,
+                               const int32_t* ray_off, const int32_t* ray_cnt, const int32_t* out_step, float* T,
+                               float* rgb, float* depth, float* acc, int32_t* next_step, uint8_t* alive,
+                               uint8_t* exhausted, float step_size, float t_thresh, unsigned long long* consumed,
+                               int32_t* ray_used, const float* t_shift, hipStream_t stream) {
+  if (N == 0) return 0;
+  MarchCompArgs a{raw, rays, N, t_table, ray_off, ray_cnt, out_step,
+                  {T, rgb, depth, acc, next_step, alive, exhausted}, step_size, t_thresh, consumed, ray_used, t_shift};
+  if (t_shift) hipLaunchKernelGGL(march_composite_kernel<true>, grid1(N), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(march_composite_kernel<false>, grid1(N), dim3(256), 0, stream, a);
+  return check_launch("nerf_march_composite");
 }
 
 int nerf_march_composite_used(const float* raw, const float* rays, int64_t N, const float* t_table,
@@ -1105,11 +1204,8 @@ int nerf_march_composite_used(const float* raw, const float* rays, int64_t N, co
                               float* rgb, float* depth, float* acc, int32_t* next_step, uint8_t* alive,
                               uint8_t* exhausted, float step_size, float t_thresh, unsigned long long* consumed,
                               int32_t* ray_used, hipStream_t stream) {
-  if (N == 0) return 0;
-  MarchCompArgs a{raw, rays, N, t_table, ray_off, ray_cnt, out_step,
-                  {T, rgb, depth, acc, next_step, alive, exhausted}, step_size, t_thresh, consumed, ray_used};
-  hipLaunchKernelGGL(march_composite_kernel, grid1(N), dim3(256), 0, stream, a);
-  return check_launch("nerf_march_composite");
+  return nerf_march_composite_shift(raw, rays, N, t_table, ray_off, ray_cnt, out_step, T, rgb, depth, acc, next_step,
+                                    alive, exhausted, step_size, t_thresh, consumed, ray_used, nullptr, stream);
 }
 
 int nerf_march_composite(const float* raw, const float* rays, int64_t N, const float* t_table, const int32_t* ray_off,
@@ -1120,9 +1216,10 @@ int nerf_march_composite(const float* raw, const float* rays, int64_t N, const f
                                    alive, exhausted, step_size, t_thresh, consumed, nullptr, stream);
 }
 
-int nerf_march_segments(const float* rays, int64_t N, const float* t_table, int n_steps, const uint8_t* grid, int res,
-                        const uint8_t* macro, const float* bbox_host, const int32_t* seg_off, int32_t* out_ray,
-                        int32_t* out_step, float* out_pts, hipStream_t stream) {
+int nerf_march_segments_shift(const float* rays, int64_t N, const float* t_table, int n_steps, const uint8_t* grid,
+                              int res, const uint8_t* macro, const float* bbox_host, const int32_t* seg_off,
+                              int32_t* out_ray, int32_t* out_step, float* out_pts, const float* t_shift,
+                              hipStream_t stream) {
   NERF_REQUIRE(N >= 0 && n_steps >= 0 && res > 1 && bbox_host, "nerf_march_segments: bad arguments");
   NERF_REQUIRE(n_steps < 65536, "nerf_march_segments: needs n_steps < 65536 (the one-pass march's step range)");
   NERF_REQUIRE(seg_off, "nerf_march_segments: seg_off is null");
@@ -1130,38 +1227,64 @@ int nerf_march_segments(const float* rays, int64_t N, const float* t_table, int 
   NERF_REQUIRE(rays && grid && (t_table || n_steps == 0), "nerf_march_segments: null pointer");
   MarchGatherArgs a{rays, N, t_table, n_steps, grid, res, macro, make_bbox(bbox_host), 0, 0, 0.f,
                     {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
-                    nullptr, nullptr, out_ray, out_step, out_pts, nullptr, nullptr, 0};
-  hipLaunchKernelGGL(march_segments_kernel, grid1(N), dim3(256), 0, stream, a, seg_off);
+                    nullptr, nullptr, out_ray, out_step, out_pts, nullptr, nullptr, 0, t_shift};
+  if (t_shift) hipLaunchKernelGGL(march_segments_kernel<true>, grid1(N), dim3(256), 0, stream, a, seg_off);
+  else hipLaunchKernelGGL(march_segments_kernel<false>, grid1(N), dim3(256), 0, stream, a, seg_off);
   return check_launch("nerf_march_segments");
+}
+
+int nerf_march_segments(const float* rays, int64_t N, const float* t_table, int n_steps, const uint8_t* grid, int res,
+                        const uint8_t* macro, const float* bbox_host, const int32_t* seg_off, int32_t* out_ray,
+                        int32_t* out_step, float* out_pts, hipStream_t stream) {
+  return nerf_march_segments_shift(rays, N, t_table, n_steps, grid, res, macro, bbox_host, seg_off, out_ray, out_step,
+                                   out_pts, nullptr, stream);
 }
 
 static inline dim3 seg_grid(int64_t N) { return dim3((unsigned)((N + SEG_WAVES - 1) / SEG_WAVES)); }
 
-int nerf_march_seg_composite_fwd(const float* raw, const float* rays, int64_t N, const float* t_table,
-                                 const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
-                                 float* rgb, float* depth, float* acc, hipStream_t stream) {
+int nerf_march_seg_composite_fwd_shift(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                       const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                       float* rgb, float* depth, float* acc, const float* t_shift,
+                                       hipStream_t stream) {
   NERF_REQUIRE(N >= 0, "nerf_march_seg_composite_fwd: N must be >= 0");
   NERF_REQUIRE(seg_off, "nerf_march_seg_composite_fwd: seg_off is null");
   if (N == 0) return 0;
   NERF_REQUIRE(rays && rgb && depth && acc, "nerf_march_seg_composite_fwd: null pointer");
   SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white, rgb, depth, acc,
-                nullptr, nullptr, nullptr, nullptr};
-  hipLaunchKernelGGL(march_seg_fwd_kernel, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+                nullptr, nullptr, nullptr, nullptr, t_shift};
+  if (t_shift) hipLaunchKernelGGL(march_seg_fwd_kernel<true>, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  else hipLaunchKernelGGL(march_seg_fwd_kernel<false>, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
   return check_launch("nerf_march_seg_composite_fwd");
+}
+
+int nerf_march_seg_composite_fwd(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                 const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                 float* rgb, float* depth, float* acc, hipStream_t stream) {
+  return nerf_march_seg_composite_fwd_shift(raw, rays, N, t_table, seg_off, out_step, step_size, white, rgb, depth,
+                                            acc, nullptr, stream);
+}
+
+int nerf_march_seg_composite_bwd_shift(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                       const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                       const float* g_rgb, const float* g_depth, const float* g_acc, float* g_raw,
+                                       const float* t_shift, hipStream_t stream) {
+  NERF_REQUIRE(N >= 0, "nerf_march_seg_composite_bwd: N must be >= 0");
+  NERF_REQUIRE(seg_off, "nerf_march_seg_composite_bwd: seg_off is null");
+  if (N == 0) return 0;
+  NERF_REQUIRE(rays, "nerf_march_seg_composite_bwd: null pointer");
+  SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white, nullptr, nullptr, nullptr,
+                g_rgb, g_depth, g_acc, g_raw, t_shift};
+  if (t_shift) hipLaunchKernelGGL(march_seg_bwd_kernel<true>, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  else hipLaunchKernelGGL(march_seg_bwd_kernel<false>, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  return check_launch("nerf_march_seg_composite_bwd");
 }
 
 int nerf_march_seg_composite_bwd(const float* raw, const float* rays, int64_t N, const float* t_table,
                                  const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
                                  const float* g_rgb, const float* g_depth, const float* g_acc, float* g_raw,
                                  hipStream_t stream) {
-  NERF_REQUIRE(N >= 0, "nerf_march_seg_composite_bwd: N must be >= 0");
-  NERF_REQUIRE(seg_off, "nerf_march_seg_composite_bwd: seg_off is null");
-  if (N == 0) return 0;
-  NERF_REQUIRE(rays, "nerf_march_seg_composite_bwd: null pointer");
-  SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white, nullptr, nullptr, nullptr,
-                g_rgb, g_depth, g_acc, g_raw};
-  hipLaunchKernelGGL(march_seg_bwd_kernel, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
-  return check_launch("nerf_march_seg_composite_bwd");
+  return nerf_march_seg_composite_bwd_shift(raw, rays, N, t_table, seg_off, out_step, step_size, white, g_rgb, g_depth,
+                                            g_acc, g_raw, nullptr, stream);
 }
 
 int nerf_march_budget(const int32_t* ray_used, int64_t N, int64_t budget, int32_t* seg_off, int64_t* keep,

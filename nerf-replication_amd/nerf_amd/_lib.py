@@ -74,6 +74,14 @@ SIGNATURES = {
     "nerf_march_seg_composite_fwd": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p]),
     "nerf_march_seg_composite_bwd": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _p]),
     "nerf_march_budget": (_i32, [_p, _i64, _i64, _p, _p, _p]),
+    "nerf_march_jitter": (_i32, [_i64, _f32, _u64, _u64, _p, _p]),
+    "nerf_march_gather_shift": (_i32, [_p, _i64, _p, _i32, _p, _i32, _p, _p, _i32, _i32, _f32, _p, _p, _p, _p, _p, _p,
+                                       _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "nerf_march_composite_shift": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f32, _f32, _p, _p,
+                                          _p, _p]),
+    "nerf_march_segments_shift": (_i32, [_p, _i64, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "nerf_march_seg_composite_fwd_shift": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _p]),
+    "nerf_march_seg_composite_bwd_shift": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _p, _p]),
     "nerf_grid_update_points": (_i32, [_i32, _p, _u64, _u64, _u64, _u64, _i64, _i64, _p, _p, _p]),
     "nerf_grid_update_apply": (_i32, [_p, _p, _i64, _i32, _f32, _p, _p]),
     "nerf_grid_update_workspace_bytes": (_i64, [_i32]),

@@ -847,11 +847,42 @@ def mlp_count(packer: PackedMLP, pts: torch.Tensor, viewdirs: torch.Tensor, dir_
     return raw
 
 
+def march_jitter(n: int, step_size: float, seed: int, offset: int, device) -> torch.Tensor:
+    """Per-ray shifts of the march steps (nerf_march_jitter) -> float32 [n] in [0, step_size):
+    the Philox uniform of (ray, offset) under ``seed``, the stratified sampler's stream, times
+    step_size.  One launch; the ``t_shift`` of march / march_segments / march_grad."""
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"march_jitter: n must be >= 0, got {n}")
+    out = torch.empty(n, dtype=torch.float32, device=device)
+    if n > 0:
+        check(lib().nerf_march_jitter(n, float(step_size), int(seed), int(offset), ptr(out), stream_of(out)),
+              "nerf_march_jitter")
+    return out
+
+
+def _shift_arg(t_shift: Optional[torch.Tensor], rays: torch.Tensor) -> Optional[torch.Tensor]:
+    """A per-ray shift as the kernels read it: fp32, contiguous, [N], on the rays' device (no
+    conversion: both passes of a differentiable march must read the very same values)."""
+    if t_shift is None:
+        return None
+    if not torch.is_tensor(t_shift) or t_shift.dtype != torch.float32:
+        raise TypeError("t_shift must be a float32 tensor, got "
+                        f"{t_shift.dtype if torch.is_tensor(t_shift) else type(t_shift).__name__}")
+    if t_shift.device != rays.device:
+        raise ValueError(f"t_shift is on {t_shift.device}, the rays on {rays.device}")
+    if t_shift.dim() != 1 or t_shift.shape[0] != rays.shape[0] or not t_shift.is_contiguous():
+        raise ValueError(f"t_shift must be contiguous [{rays.shape[0]}] (one shift per ray), "
+                         f"got {tuple(t_shift.shape)}")
+    return t_shift
+
+
 def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: torch.Tensor, step_size: float = 0.005,
           t_thresh: float = 1e-4, bbox=SCENE_BBOX, white_bkgd: bool = True, dtype=F32,
           t_table: Optional[torch.Tensor] = None, k_schedule=(12, 24, 48, 96, 192, 384, 768),
           round_bytes: int = 1 << 31, k_low: int = 8, t_split: float = 0.9, sync_every: int = 4,
-          use_macro: bool = True, one_pass: bool = True, k_low_grow: int = 8, return_used: bool = False):
+          use_macro: bool = True, one_pass: bool = True, k_low_grow: int = 8, return_used: bool = False,
+          t_shift: Optional[torch.Tensor] = None):
     """Grid-accelerated march with early termination -> dict(rgb_map_f, depth_map_f,
     acc_map_f, n_queried, n_evaluated, rounds).
 
@@ -879,13 +910,17 @@ def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: 
     comes from PyTorch's caching allocator, so consecutive frames (and in-training
     validation) reuse one block rather than allocating it again.  With ``return_used`` the
     result also carries ``ray_used`` (int32 [N]): the points composited per ray, summed over the
-    rounds (ray_used.sum() == n_queried); the other outputs are the same bit for bit."""
+    rounds (ray_used.sum() == n_queried); the other outputs are the same bit for bit.  ``t_shift``
+    (float32 [N], ops.march_jitter) moves ray r's steps to t_table + t_shift[r] (one rounded fp32
+    add per step, the skip still exact); None is the table as it is, with the same launches."""
     return _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table, k_schedule,
-                  round_bytes, k_low, t_split, sync_every, use_macro, one_pass, k_low_grow, return_used)[0]
+                  round_bytes, k_low, t_split, sync_every, use_macro, one_pass, k_low_grow, return_used,
+                  t_shift=t_shift)[0]
 
 
 def _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table, k_schedule,
-           round_bytes, k_low, t_split, sync_every, use_macro, one_pass, k_low_grow, return_used, budget=None):
+           round_bytes, k_low, t_split, sync_every, use_macro, one_pass, k_low_grow, return_used, budget=None,
+           t_shift=None):
     """march() -> (its result, the walk's inputs for a second pass over the same rays: the
     contiguous rays, the t table, the uint8 grid, its macro blocks, the unit view directions).
     With ``budget`` (needs return_used) the per-ray counts are also cut at that many points
@@ -893,6 +928,7 @@ def _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd,
     numbers: no further synchronisation): the result gains seg_off (int32 [N+1]), rays_kept, n_points."""
     rays = _f32c(rays.reshape(-1, 6), "rays")
     dev, N = rays.device, rays.shape[0]
+    t_shift = _shift_arg(t_shift, rays)
     L = lib()
     s = stream_of(rays)
     if N == 0:
@@ -949,17 +985,17 @@ def _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd,
         kl = k_low if k_low_grow <= 0 or rounds < k_low_grow else k_low << min(20, rounds - k_low_grow + 1)
         kl = max(1, min(kl, K))
         counters.zero_()
-        check(L.nerf_march_gather(ptr(rays), N, ptr(t_table), n_steps, ptr(g), res, ptr(macro), bb, K, int(kl),
-                                  float(t_split),
-                                  ptr(T), ptr(rgb), ptr(depth), ptr(acc), ptr(nxt), ptr(alive), ptr(exh),
-                                  ptr(counters), stats[1:].data_ptr(), ptr(start), ptr(out_ray), ptr(out_step),
-                                  ptr(out_pts), ptr(off), ptr(cnt), cap, s), "nerf_march_gather")
+        check(L.nerf_march_gather_shift(ptr(rays), N, ptr(t_table), n_steps, ptr(g), res, ptr(macro), bb, K, int(kl),
+                                        float(t_split),
+                                        ptr(T), ptr(rgb), ptr(depth), ptr(acc), ptr(nxt), ptr(alive), ptr(exh),
+                                        ptr(counters), stats[1:].data_ptr(), ptr(start), ptr(out_ray), ptr(out_step),
+                                        ptr(out_pts), ptr(off), ptr(cnt), cap, ptr(t_shift), s), "nerf_march_gather")
         with torch.no_grad():
             mlp_count(packer, out_pts, vd, out_ray, counters, raw, dtype)
-        check(L.nerf_march_composite_used(ptr(raw), ptr(rays), N, ptr(t_table), ptr(off), ptr(cnt), ptr(out_step),
-                                          ptr(T), ptr(rgb), ptr(depth), ptr(acc), ptr(nxt), ptr(alive), ptr(exh),
-                                          float(step_size), float(t_thresh), stats.data_ptr(), ptr(used), s),
-              "nerf_march_composite")
+        check(L.nerf_march_composite_shift(ptr(raw), ptr(rays), N, ptr(t_table), ptr(off), ptr(cnt), ptr(out_step),
+                                           ptr(T), ptr(rgb), ptr(depth), ptr(acc), ptr(nxt), ptr(alive), ptr(exh),
+                                           float(step_size), float(t_thresh), stats.data_ptr(), ptr(used),
+                                           ptr(t_shift), s), "nerf_march_composite")
         if rounds >= live_hist.numel():
             live_hist = torch.cat([live_hist, torch.zeros_like(live_hist)])
         live_hist[rounds:rounds + 1].copy_(counters[1:2])
@@ -986,51 +1022,57 @@ class _MarchSegComposite(torch.autograd.Function):
     differentiable in raw, every point of a segment used (the march decided which, without grad)."""
 
     @staticmethod
-    def forward(ctx, raw, rays, t_table, seg_off, out_step, step_size, white):
+    def forward(ctx, raw, rays, t_table, seg_off, out_step, step_size, white, t_shift=None):
         raw = _f32c(raw.reshape(-1, 4), "raw")
         N, dev = rays.shape[0], rays.device
+        t_shift = _shift_arg(t_shift, rays)
         rgb = torch.empty(N, 3, device=dev, dtype=torch.float32)
         depth = torch.empty(N, device=dev, dtype=torch.float32)
         acc = torch.empty(N, device=dev, dtype=torch.float32)
         M = raw.shape[0]
         # bytes: raw 16 B + step 4 B per point; ray 24 B, offsets 4 B, rgb/depth/acc 20 B per ray
         with kernel_timer("march_seg_composite_fwd", 20 * M + 48 * N, detail=True):
-            check(lib().nerf_march_seg_composite_fwd(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step),
-                                                     float(step_size), int(bool(white)), ptr(rgb), ptr(depth),
-                                                     ptr(acc), stream_of(rays)), "nerf_march_seg_composite_fwd")
+            check(lib().nerf_march_seg_composite_fwd_shift(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
+                                                           ptr(out_step), float(step_size), int(bool(white)),
+                                                           ptr(rgb), ptr(depth), ptr(acc), ptr(t_shift),
+                                                           stream_of(rays)), "nerf_march_seg_composite_fwd")
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(raw, rays, t_table, seg_off, out_step)
+        ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift)
         ctx.step_size, ctx.white = float(step_size), int(bool(white))
         return rgb, depth, acc
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth, g_acc):
         if g_rgb is None and g_depth is None and g_acc is None:
-            return (None,) * 7
-        raw, rays, t_table, seg_off, out_step = ctx.saved_tensors
+            return (None,) * 8
+        raw, rays, t_table, seg_off, out_step, t_shift = ctx.saved_tensors
         N, M = rays.shape[0], raw.shape[0]
         g = [None if t is None else _f32c(t, "cotangent") for t in (g_rgb, g_depth, g_acc)]
         g_raw = torch.empty_like(raw)
         # bytes: raw 16 B + step 4 B read twice (entry transmittances, then the reverse walk), d_raw 16 B written
         with kernel_timer("march_seg_composite_bwd", 56 * M + 48 * N, detail=True):
-            check(lib().nerf_march_seg_composite_bwd(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step),
-                                                     ctx.step_size, ctx.white, ptr(g[0]), ptr(g[1]), ptr(g[2]),
-                                                     ptr(g_raw), stream_of(rays)), "nerf_march_seg_composite_bwd")
-        return (g_raw,) + (None,) * 6
+            check(lib().nerf_march_seg_composite_bwd_shift(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
+                                                           ptr(out_step), ctx.step_size, ctx.white, ptr(g[0]),
+                                                           ptr(g[1]), ptr(g[2]), ptr(g_raw), ptr(t_shift),
+                                                           stream_of(rays)), "nerf_march_seg_composite_bwd")
+        return (g_raw,) + (None,) * 7
 
 
 def march_segments(rays: torch.Tensor, t_table: torch.Tensor, grid_u8: torch.Tensor, macro: Optional[torch.Tensor],
-                   seg_off: torch.Tensor, M: int, bbox=SCENE_BBOX):
+                   seg_off: torch.Tensor, M: int, bbox=SCENE_BBOX, t_shift: Optional[torch.Tensor] = None):
     """Every ray's first seg_off[r+1] - seg_off[r] occupied steps, contiguous in ray order
-    (nerf_march_segments) -> out_ray [M] int32, out_step [M] int32 (-1: surplus), out_pts [M,3]."""
+    (nerf_march_segments) -> out_ray [M] int32, out_step [M] int32 (-1: surplus), out_pts [M,3].
+    ``t_shift`` (float32 [N]): ray r walks the depths t_table + t_shift[r]."""
     dev, N = rays.device, rays.shape[0]
+    t_shift = _shift_arg(t_shift, rays)
     out_ray = torch.empty(M, dtype=torch.int32, device=dev)
     out_step = torch.empty(M, dtype=torch.int32, device=dev)
     out_pts = torch.empty(M, 3, device=dev)
     if M > 0:
-        check(lib().nerf_march_segments(ptr(rays), N, ptr(t_table), t_table.numel(), ptr(grid_u8),
-                                        int(grid_u8.shape[0]), ptr(macro), _bbox_arr(bbox), ptr(seg_off), ptr(out_ray),
-                                        ptr(out_step), ptr(out_pts), stream_of(rays)), "nerf_march_segments")
+        check(lib().nerf_march_segments_shift(ptr(rays), N, ptr(t_table), t_table.numel(), ptr(grid_u8),
+                                              int(grid_u8.shape[0]), ptr(macro), _bbox_arr(bbox), ptr(seg_off),
+                                              ptr(out_ray), ptr(out_step), ptr(out_pts), ptr(t_shift),
+                                              stream_of(rays)), "nerf_march_segments")
     return out_ray, out_step, out_pts
 
 
@@ -1058,7 +1100,8 @@ def march_budget(ray_used: torch.Tensor, budget: int, keep: Optional[torch.Tenso
 def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: torch.Tensor,
                step_size: float = 0.005, t_thresh: float = 1e-4, bbox=SCENE_BBOX, white_bkgd: bool = True, dtype=F32,
                t_table: Optional[torch.Tensor] = None, k_schedule=(12, 24, 48, 96, 192, 384, 768),
-               round_bytes: int = 1 << 31, use_macro: bool = True, max_points: Optional[int] = None):
+               round_bytes: int = 1 << 31, use_macro: bool = True, max_points: Optional[int] = None,
+               t_shift: Optional[torch.Tensor] = None):
     """march() whose maps carry an autograd graph back to the packer's parameters: what the
     reference's render_accelerated gives when it is called with autograd on.  Two passes, in the
     spirit of the detached sample_pdf of render().  Pass A is march() itself, without gradient:
@@ -1076,7 +1119,10 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
     on rays[:rays_kept] makes, so rows < rays_kept and their gradient equal that call's bit for bit.
     The maps keep N rows: rows >= rays_kept hold pass A's values and carry no gradient.  n_queried
     stays pass A's count over all N rays.  B must be at least the march's steps (a ray can need them
-    all), so that rays_kept >= 1 for N >= 1; the two numbers ride on pass A's host read."""
+    all), so that rays_kept >= 1 for N >= 1; the two numbers ride on pass A's host read.
+
+    ``t_shift`` (float32 [N], ops.march_jitter): ray r's steps are t_table + t_shift[r] in both
+    passes, which read the same tensor (under a budget, its first rays_kept entries in pass B)."""
     if max_points is not None:
         max_points = int(max_points)
         n_steps = (t_table.numel() if t_table is not None
@@ -1086,7 +1132,8 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
                              f"them all), 2^31 - 1], got {max_points}")
     with torch.no_grad():
         out, walk = _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table,
-                           k_schedule, round_bytes, 8, 0.9, 4, use_macro, True, 8, True, max_points)
+                           k_schedule, round_bytes, 8, 0.9, 4, use_macro, True, 8, True, max_points,
+                           t_shift=t_shift)
     used = out.pop("ray_used")
     seg_off = out.pop("seg_off", None)
     if walk is None:  # no rays
@@ -1101,9 +1148,11 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
         n_keep, M = out["rays_kept"], out["n_points"]
     if n_keep < N:  # pass B over the kept rays alone: the first n_keep + 1 offsets are their exclusive prefix sum
         rays_c, vd = rays_c[:n_keep], vd[:n_keep]
-    out_ray, out_step, out_pts = march_segments(rays_c, t_tab, g8, macro, seg_off, M, bbox)
+        t_shift = None if t_shift is None else t_shift[:n_keep]
+    out_ray, out_step, out_pts = march_segments(rays_c, t_tab, g8, macro, seg_off, M, bbox, t_shift)
     raw = mlp(packer, out_pts, vd, 1, out_ray, dtype)
-    maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd))
+    maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd),
+                                    t_shift)
     for k, v in zip(("rgb_map_f", "depth_map_f", "acc_map_f"), maps):
         out[k] = v if n_keep == N else torch.cat([v, out[k][n_keep:]], 0)  # (the dropped rows: pass A's, no graph)
     return out

@@ -39,6 +39,16 @@ FRAGILE_Z_TOL = 0.0
 TRAIN_K_SCHEDULE = (96, 384, 768)
 
 
+def march_jitter_setting(task_arg) -> bool:
+    """task_arg.train_march_jitter (bool, default false): jittered march steps in the training march."""
+    v = task_arg.get("train_march_jitter", False)
+    if v is None:
+        return False
+    if not isinstance(v, bool):
+        raise ValueError(f"task_arg.train_march_jitter must be true or false, got {v!r}")
+    return v
+
+
 class Renderer:
     def __init__(self, net):
         self.net = net
@@ -210,21 +220,32 @@ class Renderer:
         concatenated, as render() does; no device-wide synchronisation (render_time is host time).
         With a point budget (self.max_points) the whole batch is ONE march instead: chunk_size does not
         split it -- the differentiable pass is bounded by max_points and the no-grad pass by the march's
-        round_bytes -- and the result also carries rays_kept / n_points (ops.march_grad(max_points=))."""
+        round_bytes -- and the result also carries rays_kept / n_points (ops.march_grad(max_points=)).
+        With task_arg.train_march_jitter every ray's steps are shifted by a random fraction of a step
+        (ops.march_jitter): ONE draw for the whole batch, from this renderer's seed and call counter,
+        before the split into chunks (a chunked step equals the unchunked one), returned as t_shift.
+        Only this path jitters: the no-grad march of render_accelerated never does."""
         ta = cfg.task_arg
         start = time.time()
         chunk = self._chunk(True)
         packer = self.net.model_fine.packer()
         sched = tuple(int(k) for k in ta.get("train_k_schedule", TRAIN_K_SCHEDULE))
+        t_shift = None
+        if march_jitter_setting(ta):
+            off, _ = self._next_offsets()
+            t_shift = ops.march_jitter(rays_flat.shape[0], float(ta.render_step_size), self._seed, off,
+                                       rays_flat.device)
         if self.max_points:
             out = ops.march_grad(packer, rays_flat, near, far, self.occupancy_grid,
                                  step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
                                  bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
-                                 k_schedule=sched, max_points=int(self.max_points))
+                                 k_schedule=sched, max_points=int(self.max_points), t_shift=t_shift)
             keys = ("rgb_map_f", "depth_map_f", "acc_map_f", "n_queried", "n_evaluated", "rounds", "rays_kept",
                     "n_points")
             ret = {k: out[k] for k in keys}
             ret["render_time"] = time.time() - start
+            if t_shift is not None:
+                ret["t_shift"] = t_shift
             return ret
         maps = {"rgb_map_f": [], "depth_map_f": [], "acc_map_f": []}
         counts = {"n_queried": 0, "n_evaluated": 0, "rounds": 0}
@@ -232,7 +253,7 @@ class Renderer:
             out = ops.march_grad(packer, rays_flat[i:i + chunk], near, far, self.occupancy_grid,
                                  step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
                                  bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
-                                 k_schedule=sched)
+                                 k_schedule=sched, t_shift=None if t_shift is None else t_shift[i:i + chunk])
             for k, v in maps.items():
                 v.append(out[k])
             for k in counts:
@@ -240,6 +261,8 @@ class Renderer:
         ret = {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in maps.items()}
         ret["render_time"] = time.time() - start
         ret.update(counts)
+        if t_shift is not None:
+            ret["t_shift"] = t_shift
         return ret
 
     def render_accelerated(self, batch):

@@ -31,6 +31,12 @@ follows its own count with no collective, so the all-reduce averages per-rank ME
 different ray counts (each rank weighs 1 / world, not its rays); the online grids stay bit-identical
 (they depend on the weights only).  save_grid() / load_grid() also carry the count
 (<model_dir>/ray_budget_state.pt).
+
+``task_arg.train_march_jitter: true`` (default false; only with ``train_renderer: accelerated``, either
+``train_grid``, with or without a point budget) shifts every ray's march steps by a random fraction of a
+step in each training forward (Renderer._render_accelerated_grad; ret["t_shift"]).  Validation and every
+other no-grad march keep the fixed steps.  The renderer's seed contains the rank, so ranks draw different
+shifts; the stream restarts with the renderer's call counter on resume, as the ``perturb`` stream does.
 """
 import os
 
@@ -42,7 +48,7 @@ from nerf_amd import ops
 from src.config import cfg
 from src.models.nerf.renderer.online_grid import OnlineGrid, grid_update_settings
 from src.models.nerf.renderer.ray_budget import RayBudget
-from src.models.nerf.renderer.volume_renderer import Renderer
+from src.models.nerf.renderer.volume_renderer import Renderer, march_jitter_setting
 
 TRAIN_RENDERERS = ("hierarchical", "accelerated")
 TRAIN_GRIDS = ("file", "online")
@@ -70,6 +76,10 @@ class NetworkWrapper(nn.Module):
         self.train_grid = str(cfg.task_arg.get("train_grid", "file") or "file")
         if self.train_grid not in TRAIN_GRIDS:
             raise ValueError(f"task_arg.train_grid must be one of {TRAIN_GRIDS}, got {self.train_grid!r}")
+        self.march_jitter = march_jitter_setting(cfg.task_arg)
+        if self.march_jitter and self.train_renderer != "accelerated":
+            raise ValueError("task_arg.train_march_jitter: true jitters the steps of train_renderer: accelerated; "
+                             f"with train_renderer: {self.train_renderer} the samples follow task_arg.perturb")
         self.ray_budget = RayBudget.from_config(cfg.task_arg)  # (None: point_budget.target 0, the fixed train_rays)
         if self.ray_budget is not None:
             self.renderer.max_points = self.ray_budget.max_points

@@ -2,6 +2,7 @@
 from-scratch run through the march converges against the hierarchical one.
 
     python tools/grid_train_bench.py [--tiers fp32,bf16x3f] [--out profiles/r8/online_grid.json]
+    python tools/grid_train_bench.py --jitter [--out profiles/r10/march_jitter.json]
 
 One process, HIP events on the compute stream, medians.
 
@@ -17,6 +18,8 @@ convergence the procedural scene (src/datasets/nerf/synthetic.py), seed-0 init, 
             online-accelerated against hierarchical, held-out PSNR (4 views of 100x100; the online run
             rendered through the march with its live grid, the hierarchical one with render()) against
             the wall-clock spent in training steps (evaluation excluded), per tier.
+--jitter    the convergence part alone, online-accelerated with task_arg.train_march_jitter off and on
+            (same scene, seed, ray stream, steps and tiers), merged into --out under "convergence".
 """
 import argparse
 import json
@@ -57,8 +60,12 @@ def main():
     ap.add_argument("--steps", type=int, default=2000, help="convergence: training steps per run")
     ap.add_argument("--every", type=int, default=250, help="convergence: steps between held-out renders")
     ap.add_argument("--rays", type=int, default=4096, help="convergence: rays per step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r8", "online_grid.json"))
+    ap.add_argument("--jitter", action="store_true",
+                    help="convergence only: online-accelerated with train_march_jitter off and on")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", *(("r10", "march_jitter.json") if a.jitter else ("r8", "online_grid.json")))
     from nerf_amd import ops
     from src.config import cfg
     from src.datasets.nerf.blender import Dataset
@@ -102,7 +109,7 @@ def main():
 
     # ---- update cost ---------------------------------------------------------------------------------
     ta.perturb = 0
-    for dtype in a.tiers.split(","):
+    for dtype in () if a.jitter else a.tiers.split(","):
         packer = fixture_net(dtype).model_fine.packer()
         g = OnlineGrid(128, float(ta.occupancy_grid_threshold), bbox, dev, **DEFAULTS)
         for _ in range(2):
@@ -119,7 +126,7 @@ def main():
         print("update", dtype, json.dumps(result["update"][dtype]), flush=True)
 
     # ---- the step, online (amortised) against file mode ----------------------------------------------
-    for dtype in a.tiers.split(","):
+    for dtype in () if a.jitter else a.tiers.split(","):
         ta.mlp_dtype = dtype
         stacks = {}
         for mode in ("file", "online"):
@@ -174,9 +181,12 @@ def main():
     ta.train_rays = a.rays
     for dtype in a.convergence_tiers.split(","):
         result["convergence"][dtype] = {"rays_per_step": a.rays, "steps": a.steps, "all_white_psnr_db": round(white_db, 3)}
-        for mode in ("online_accelerated", "hierarchical"):
+        modes = ("online_accelerated", "online_accelerated_jitter") if a.jitter else ("online_accelerated",
+                                                                                      "hierarchical")
+        for mode in modes:
             ta.mlp_dtype = dtype
             ta.perturb = 1
+            ta.train_march_jitter = mode == "online_accelerated_jitter"
             ta.train_renderer, ta.train_grid = ("accelerated", "online") if mode != "hierarchical" else ("hierarchical",
                                                                                                          "file")
             torch.manual_seed(0)
@@ -219,8 +229,13 @@ def main():
             del net, trainer, opt
             torch.cuda.empty_cache()
     reset_modes()
+    ta.train_march_jitter = False
 
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    if a.jitter:  # the jitter file also holds the cost measurements of other tools: only this part is replaced
+        conv = result["convergence"]
+        result = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        result.update(device=torch.cuda.get_device_name(0), convergence=conv)
     with open(a.out, "w") as f:
         json.dump(result, f, indent=1)
         f.write("\n")
