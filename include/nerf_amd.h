@@ -306,6 +306,30 @@ int nerf_march_seg_composite_bwd_shift(const float* raw, const float* rays, int6
                                        const float* g_rgb, const float* g_depth, const float* g_acc, float* g_raw,
                                        const float* t_shift, hipStream_t stream);
 
+/* ---- (a13) distortion of a ray's weights (training regulariser) ----------------------------------------
+ * The segment compositing pair with one more output per ray, Mip-NeRF 360's distortion loss on depths
+ * normalised by the march's range (inv_range = 1 / (far - near), fp32, from the host):
+ *   dist[r] = inv_range * ( sum_i sum_j w_i w_j |t_i - t_j|  +  (step_size / 3) * sum_i w_i^2 )
+ * over the points of ray r's segment, w_k = T_k alpha_k the compositor's own weights (0 on a surplus
+ * point), t_k the depth depth_map_f uses (t_table[out_step[k]] + t_shift[r]), every sample an interval
+ * step_size wide.  Steps increase within a segment, so the kernels evaluate it in O(n) with prefix sums
+ * in double.  The forward also writes the ray's totals (sum w, sum w t) as two doubles into totals
+ * [N,2] (caller-owned), which the backward reads back; an empty segment gives 0 and (0, 0).  rgb, depth
+ * and acc are the bits of nerf_march_seg_composite_fwd_shift.  The backward adds g_dist[r] d dist[r] /
+ * d w_k to the per-point cotangent of the weights (g_dist null = 0: the bits of _bwd_shift's g_raw).
+ * t_shift may be null.  Deterministic: lanes first, then chunks in order; no atomics, no workspace
+ * beyond totals, no allocation, no host sync.  N == 0 is a no-op; a null seg_off / dist / totals or an
+ * inv_range that is not finite and > 0 is -22 before any launch. */
+int nerf_march_seg_composite_fwd_dist(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                      const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                      float* rgb, float* depth, float* acc, const float* t_shift, float inv_range,
+                                      float* dist, double* totals, hipStream_t stream);
+int nerf_march_seg_composite_bwd_dist(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                      const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                      const float* g_rgb, const float* g_depth, const float* g_acc,
+                                      const float* t_shift, float inv_range, const float* g_dist,
+                                      const double* totals, float* g_raw, hipStream_t stream);
+
 /* ---- (a12) point budget: pass A's counts -> pass B's segments, cut at a budget of points ---------------
  * ray_used[N] (int32, >= 0) -> seg_off[N+1] (int32) and keep[2] (int64, device):
  * P[r] = sum_{q<r} ray_used[q] in 64-bit;  n_keep = the largest r in [0, N] with P[r] <= budget;

@@ -14,6 +14,8 @@
 // but never composited, so outputs are those of the step-by-step march.
 #include "common.h"
 
+#include <cmath>
+
 namespace nerf {
 
 struct BBox { float mn[3], mx[3]; };
@@ -675,6 +677,12 @@ struct SegCompArgs {
   const float* g_acc;
   float* g_raw;  // [M,4]
   const float* t_shift;  // [N] the walk's per-ray shift, or null
+  // the distortion term (the DIST instantiations alone read these)
+  float inv_range;        // 1 / (far - near)
+  float* dist;            // [N] forward output
+  double* totals;         // [N,2] forward output: the ray's (sum w, sum w t)
+  const float* g_dist;    // [N] backward input (nullable = 0)
+  const double* totals_in;  // [N,2] backward input: what the forward wrote
 };
 
 constexpr int SEG_WAVES = 4;  // rays (waves) per 256-thread block
@@ -717,7 +725,14 @@ __device__ __forceinline__ float seg_sigmoid(float x) { return 1.f / (1.f + expf
 // One wave per ray, lanes on consecutive points (raw read as coalesced float4), 64 points a chunk:
 // T_k = T_in * prod_{j<k in chunk} (1 - alpha_j) by a product scan across the lanes (in double, as
 // the compositor of render()), T_in carried from chunk to chunk; every point of the segment is used.
-template <bool SHIFT>
+//
+// DIST adds the distortion of the ray's weights (Mip-NeRF 360, on depths normalised by the march's
+// range): dist = inv_range (sum_i sum_j w_i w_j |t_i - t_j| + step_size / 3 sum_i w_i^2).  The steps of
+// a segment increase, so the double sum is 2 sum_i w_i (t_i Wex_i - Sex_i) with the exclusive prefixes
+// Wex_i = sum_{j<i} w_j, Sex_i = sum_{j<i} w_j t_j: two more add scans across the lanes per chunk, in
+// double, their totals carried from chunk to chunk like T_in.  The ray's totals (W, S) go out for the
+// backward.  DIST is a template parameter like SHIFT: without it the kernel is the code it was.
+template <bool SHIFT, bool DIST>
 __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompArgs a) {
   const int64_t r = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
   if (r >= a.N) return;  // (wave-uniform)
@@ -726,6 +741,7 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompAr
   const float dist = seg_dist(a, r);
   const RayT<SHIFT> tr = ray_t<SHIFT>(a.t_table, a.t_shift, r);
   double Tin = 1.0, sr = 0.0, sg = 0.0, sb = 0.0, sd = 0.0, sa = 0.0;
+  double Wc = 0.0, Sc = 0.0, sx = 0.0;  // DIST: sum w, sum w t over the chunks before; this lane's share of dist
   for (int64_t b = beg; b < end; b += 64) {
     const int64_t k = b + l;
     int st;
@@ -733,6 +749,7 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompAr
     const double P = wave_scan_mul((double)fsub(1.f, alpha));
     double Pex = __shfl_up(P, 1, 64);
     if (l == 0) Pex = 1.0;
+    double wd = 0.0, td = 0.0;  // DIST: this lane's weight and depth (0 past the segment and on a surplus point)
     if (st >= 0) {
       const float4 rw = *(const float4*)(a.raw + k * 4);
       const double w = Tin * Pex * (double)alpha;
@@ -741,6 +758,18 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompAr
       sb += w * (double)seg_sigmoid(rw.z);
       sd += w * (double)tr(st);
       sa += w;
+      if constexpr (DIST) {
+        wd = w;
+        td = (double)tr(st);
+      }
+    }
+    if constexpr (DIST) {
+      const double w = wd, t = td, wt = w * t;
+      const double Wi = wave_scan_add(w), Si = wave_scan_add(wt);  // inclusive, within the chunk
+      const double Wex = Wc + (Wi - w), Sex = Sc + (Si - wt);
+      sx += w * (2.0 * (t * Wex - Sex) + (double)a.step_size * (1.0 / 3.0) * w);
+      Wc += shfl_d(Wi, 63);
+      Sc += shfl_d(Si, 63);
     }
     Tin *= shfl_d(P, 63);
   }
@@ -758,6 +787,14 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompAr
     a.depth[r] = (float)sd;
     a.acc[r] = acc;
   }
+  if constexpr (DIST) {
+    sx = wave_sum_d(sx);
+    if (l == 0) {
+      a.dist[r] = (float)((double)a.inv_range * sx);
+      a.totals[r * 2 + 0] = Wc;
+      a.totals[r * 2 + 1] = Sc;
+    }
+  }
 }
 
 // Backward, division-free.  With v_k = g_rgb . c_k + g_depth t_k + g_acc' (g_acc' = g_acc - sum g_rgb
@@ -769,7 +806,13 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompAr
 // 4096 points: every ray of an 800-step march) and super-chunk j's (64 chunks each); a later
 // super-chunk's chunk entries are recomputed from its own entry when the reverse walk reaches it.
 // alpha_k = 1 (exp underflow) zeroes T from k + 1 on: every later gradient is exactly 0, no 0/0.
-template <bool SHIFT>
+//
+// DIST: v_k gains g_dist d dist / d w_k = g_dist inv_range (2 [(t_k Wex_k - Sex_k) + (Ssuf_k - t_k Wsuf_k)]
+// + 2/3 step_size w_k), Wsuf / Ssuf the sums over the points after k.  The reverse walk carries the
+// suffix sums of w and w t over the chunks behind it next to C; within a chunk two add scans across the
+// lanes give the rest, and a point's exclusive prefix is the forward's saved total minus its inclusive
+// suffix, all in double.  No second pre-pass, no state per chunk.
+template <bool SHIFT, bool DIST>
 __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_bwd_kernel(SegCompArgs a) {
   const int64_t r = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
   if (r >= a.N) return;  // (wave-uniform)
@@ -793,6 +836,12 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_bwd_kernel(SegCompAr
     }
   }
   double C = 0.0;  // R at the last point of the chunk in hand
+  double Wsc = 0.0, Ssc = 0.0, Wtot = 0.0, Stot = 0.0, gx = 0.0;  // DIST: sums over the chunks after; the ray's totals
+  if constexpr (DIST) {
+    Wtot = a.totals_in[r * 2 + 0];
+    Stot = a.totals_in[r * 2 + 1];
+    gx = (a.g_dist ? (double)a.g_dist[r] : 0.0) * (double)a.inv_range;
+  }
   for (int64_t sc = nsuper - 1; sc >= 0; --sc) {
     const int64_t c0 = sc * 64, c1 = c0 + 64 < nchunks ? c0 + 64 : nchunks;
     double cT = chunkT;  // lane j: T entering chunk c0 + j
@@ -826,6 +875,22 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_bwd_kernel(SegCompAr
         cy = seg_sigmoid(rw.y);
         cz = seg_sigmoid(rw.z);
         v = gr * (double)cx + gg * (double)cy + gb * (double)cz + gd * (double)tr(st) + ga;
+      }
+      if constexpr (DIST) {
+        double w = 0.0, t = 0.0;
+        if (st >= 0) {
+          w = Tin * Pex * (double)alpha;
+          t = (double)tr(st);
+        }
+        const double wt = w * t;
+        const double Wi = wave_scan_add(w), Si = wave_scan_add(wt);  // inclusive, within the chunk
+        const double Wct = shfl_d(Wi, 63), Sct = shfl_d(Si, 63);
+        const double Wsuf = Wsc + (Wct - Wi), Ssuf = Ssc + (Sct - Si);  // over the points after this one
+        const double Wex = Wtot - (Wsuf + w), Sex = Stot - (Ssuf + wt);
+        if (st >= 0)
+          v += gx * (2.0 * ((t * Wex - Sex) + (Ssuf - t * Wsuf)) + (double)a.step_size * (2.0 / 3.0) * w);
+        Wsc += Wct;
+        Ssc += Sct;
       }
       // suffix composition: (A, B) of lane i = f_i o f_{i+1} o ... o f_63, f_j(x) = alpha_j v_j + (1 - alpha_j) x
       double A = (double)alpha * v, B = (double)om;
@@ -1251,9 +1316,9 @@ int nerf_march_seg_composite_fwd_shift(const float* raw, const float* rays, int6
   if (N == 0) return 0;
   NERF_REQUIRE(rays && rgb && depth && acc, "nerf_march_seg_composite_fwd: null pointer");
   SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white, rgb, depth, acc,
-                nullptr, nullptr, nullptr, nullptr, t_shift};
-  if (t_shift) hipLaunchKernelGGL(march_seg_fwd_kernel<true>, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
-  else hipLaunchKernelGGL(march_seg_fwd_kernel<false>, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+                nullptr, nullptr, nullptr, nullptr, t_shift, 0.f, nullptr, nullptr, nullptr, nullptr};
+  if (t_shift) hipLaunchKernelGGL((march_seg_fwd_kernel<true, false>), seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  else hipLaunchKernelGGL((march_seg_fwd_kernel<false, false>), seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
   return check_launch("nerf_march_seg_composite_fwd");
 }
 
@@ -1273,9 +1338,9 @@ int nerf_march_seg_composite_bwd_shift(const float* raw, const float* rays, int6
   if (N == 0) return 0;
   NERF_REQUIRE(rays, "nerf_march_seg_composite_bwd: null pointer");
   SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white, nullptr, nullptr, nullptr,
-                g_rgb, g_depth, g_acc, g_raw, t_shift};
-  if (t_shift) hipLaunchKernelGGL(march_seg_bwd_kernel<true>, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
-  else hipLaunchKernelGGL(march_seg_bwd_kernel<false>, seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+                g_rgb, g_depth, g_acc, g_raw, t_shift, 0.f, nullptr, nullptr, nullptr, nullptr};
+  if (t_shift) hipLaunchKernelGGL((march_seg_bwd_kernel<true, false>), seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  else hipLaunchKernelGGL((march_seg_bwd_kernel<false, false>), seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
   return check_launch("nerf_march_seg_composite_bwd");
 }
 
@@ -1285,6 +1350,46 @@ int nerf_march_seg_composite_bwd(const float* raw, const float* rays, int64_t N,
                                  hipStream_t stream) {
   return nerf_march_seg_composite_bwd_shift(raw, rays, N, t_table, seg_off, out_step, step_size, white, g_rgb, g_depth,
                                             g_acc, g_raw, nullptr, stream);
+}
+
+// The same pair with the distortion of the weights (the DIST instantiations): the forward also writes
+// dist [N] and the ray's totals (sum w, sum w t) [N,2] fp64, which the backward reads back.
+int nerf_march_seg_composite_fwd_dist(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                      const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                      float* rgb, float* depth, float* acc, const float* t_shift, float inv_range,
+                                      float* dist, double* totals, hipStream_t stream) {
+  NERF_REQUIRE(N >= 0, "nerf_march_seg_composite_fwd_dist: N must be >= 0");
+  NERF_REQUIRE(seg_off, "nerf_march_seg_composite_fwd_dist: seg_off is null");
+  NERF_REQUIRE(std::isfinite(inv_range) && inv_range > 0.f,
+               "nerf_march_seg_composite_fwd_dist: inv_range must be finite and > 0, got %g", (double)inv_range);
+  if (N == 0) return 0;
+  NERF_REQUIRE(dist, "nerf_march_seg_composite_fwd_dist: dist is null");
+  NERF_REQUIRE(totals, "nerf_march_seg_composite_fwd_dist: totals is null");
+  NERF_REQUIRE(rays && rgb && depth && acc, "nerf_march_seg_composite_fwd_dist: null pointer");
+  SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white, rgb, depth, acc,
+                nullptr, nullptr, nullptr, nullptr, t_shift, inv_range, dist, totals, nullptr, nullptr};
+  if (t_shift) hipLaunchKernelGGL((march_seg_fwd_kernel<true, true>), seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  else hipLaunchKernelGGL((march_seg_fwd_kernel<false, true>), seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  return check_launch("nerf_march_seg_composite_fwd_dist");
+}
+
+int nerf_march_seg_composite_bwd_dist(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                      const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                      const float* g_rgb, const float* g_depth, const float* g_acc,
+                                      const float* t_shift, float inv_range, const float* g_dist,
+                                      const double* totals, float* g_raw, hipStream_t stream) {
+  NERF_REQUIRE(N >= 0, "nerf_march_seg_composite_bwd_dist: N must be >= 0");
+  NERF_REQUIRE(seg_off, "nerf_march_seg_composite_bwd_dist: seg_off is null");
+  NERF_REQUIRE(std::isfinite(inv_range) && inv_range > 0.f,
+               "nerf_march_seg_composite_bwd_dist: inv_range must be finite and > 0, got %g", (double)inv_range);
+  if (N == 0) return 0;
+  NERF_REQUIRE(totals, "nerf_march_seg_composite_bwd_dist: totals is null");
+  NERF_REQUIRE(rays, "nerf_march_seg_composite_bwd_dist: null pointer");
+  SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white, nullptr, nullptr, nullptr,
+                g_rgb, g_depth, g_acc, g_raw, t_shift, inv_range, nullptr, nullptr, g_dist, totals};
+  if (t_shift) hipLaunchKernelGGL((march_seg_bwd_kernel<true, true>), seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  else hipLaunchKernelGGL((march_seg_bwd_kernel<false, true>), seg_grid(N), dim3(64 * SEG_WAVES), 0, stream, a);
+  return check_launch("nerf_march_seg_composite_bwd_dist");
 }
 
 int nerf_march_budget(const int32_t* ray_used, int64_t N, int64_t budget, int32_t* seg_off, int64_t* keep,

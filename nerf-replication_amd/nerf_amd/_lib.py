@@ -82,6 +82,10 @@ SIGNATURES = {
     "nerf_march_segments_shift": (_i32, [_p, _i64, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nerf_march_seg_composite_fwd_shift": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _p]),
     "nerf_march_seg_composite_bwd_shift": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _p, _p]),
+    "nerf_march_seg_composite_fwd_dist": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _f32, _p, _p,
+                                                 _p]),
+    "nerf_march_seg_composite_bwd_dist": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _f32, _p, _p,
+                                                 _p, _p]),
     "nerf_grid_update_points": (_i32, [_i32, _p, _u64, _u64, _u64, _u64, _i64, _i64, _p, _p, _p]),
     "nerf_grid_update_apply": (_i32, [_p, _p, _i64, _i32, _f32, _p, _p]),
     "nerf_grid_update_workspace_bytes": (_i64, [_i32]),

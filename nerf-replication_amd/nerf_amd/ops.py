@@ -1019,10 +1019,15 @@ def _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd,
 
 class _MarchSegComposite(torch.autograd.Function):
     """Compositing of per-ray segments of marched points (nerf_march_seg_composite_fwd / _bwd):
-    differentiable in raw, every point of a segment used (the march decided which, without grad)."""
+    differentiable in raw, every point of a segment used (the march decided which, without grad).
+
+    With ``inv_range`` (a positive float, 1 / (far - near)) the call goes through the ``_dist`` entry
+    points instead and returns a fourth map, the distortion of each ray's weights (float32 [N],
+    differentiable in raw); rgb, depth and acc keep their bits.  Without it: the three maps and the
+    launches they always had."""
 
     @staticmethod
-    def forward(ctx, raw, rays, t_table, seg_off, out_step, step_size, white, t_shift=None):
+    def forward(ctx, raw, rays, t_table, seg_off, out_step, step_size, white, t_shift=None, inv_range=None):
         raw = _f32c(raw.reshape(-1, 4), "raw")
         N, dev = rays.shape[0], rays.device
         t_shift = _shift_arg(t_shift, rays)
@@ -1030,32 +1035,55 @@ class _MarchSegComposite(torch.autograd.Function):
         depth = torch.empty(N, device=dev, dtype=torch.float32)
         acc = torch.empty(N, device=dev, dtype=torch.float32)
         M = raw.shape[0]
-        # bytes: raw 16 B + step 4 B per point; ray 24 B, offsets 4 B, rgb/depth/acc 20 B per ray
-        with kernel_timer("march_seg_composite_fwd", 20 * M + 48 * N, detail=True):
-            check(lib().nerf_march_seg_composite_fwd_shift(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
-                                                           ptr(out_step), float(step_size), int(bool(white)),
-                                                           ptr(rgb), ptr(depth), ptr(acc), ptr(t_shift),
-                                                           stream_of(rays)), "nerf_march_seg_composite_fwd")
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift)
         ctx.step_size, ctx.white = float(step_size), int(bool(white))
-        return rgb, depth, acc
+        ctx.inv_range = None if inv_range is None else float(inv_range)
+        if inv_range is None:
+            # bytes: raw 16 B + step 4 B per point; ray 24 B, offsets 4 B, rgb/depth/acc 20 B per ray
+            with kernel_timer("march_seg_composite_fwd", 20 * M + 48 * N, detail=True):
+                check(lib().nerf_march_seg_composite_fwd_shift(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
+                                                               ptr(out_step), float(step_size), int(bool(white)),
+                                                               ptr(rgb), ptr(depth), ptr(acc), ptr(t_shift),
+                                                               stream_of(rays)), "nerf_march_seg_composite_fwd")
+            ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift)
+            return rgb, depth, acc
+        dist = torch.empty(N, device=dev, dtype=torch.float32)
+        totals = torch.empty(N, 2, device=dev, dtype=torch.float64)
+        # bytes: the above, and dist 4 B + the totals 16 B written per ray
+        with kernel_timer("march_seg_composite_fwd_dist", 20 * M + 68 * N, detail=True):
+            check(lib().nerf_march_seg_composite_fwd_dist(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
+                                                          ptr(out_step), float(step_size), int(bool(white)),
+                                                          ptr(rgb), ptr(depth), ptr(acc), ptr(t_shift),
+                                                          ctx.inv_range, ptr(dist), ptr(totals), stream_of(rays)),
+                  "nerf_march_seg_composite_fwd_dist")
+        ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift, totals)
+        return rgb, depth, acc, dist
 
     @staticmethod
-    def backward(ctx, g_rgb, g_depth, g_acc):
-        if g_rgb is None and g_depth is None and g_acc is None:
-            return (None,) * 8
-        raw, rays, t_table, seg_off, out_step, t_shift = ctx.saved_tensors
+    def backward(ctx, *grads):
+        if all(t is None for t in grads):
+            return (None,) * 9
+        raw, rays, t_table, seg_off, out_step, t_shift = ctx.saved_tensors[:6]
         N, M = rays.shape[0], raw.shape[0]
-        g = [None if t is None else _f32c(t, "cotangent") for t in (g_rgb, g_depth, g_acc)]
+        g = [None if t is None else _f32c(t, "cotangent") for t in grads]
         g_raw = torch.empty_like(raw)
-        # bytes: raw 16 B + step 4 B read twice (entry transmittances, then the reverse walk), d_raw 16 B written
-        with kernel_timer("march_seg_composite_bwd", 56 * M + 48 * N, detail=True):
-            check(lib().nerf_march_seg_composite_bwd_shift(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
-                                                           ptr(out_step), ctx.step_size, ctx.white, ptr(g[0]),
-                                                           ptr(g[1]), ptr(g[2]), ptr(g_raw), ptr(t_shift),
-                                                           stream_of(rays)), "nerf_march_seg_composite_bwd")
-        return (g_raw,) + (None,) * 7
+        if ctx.inv_range is None:
+            # bytes: raw 16 B + step 4 B read twice (entry transmittances, then the reverse walk), d_raw 16 B written
+            with kernel_timer("march_seg_composite_bwd", 56 * M + 48 * N, detail=True):
+                check(lib().nerf_march_seg_composite_bwd_shift(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
+                                                               ptr(out_step), ctx.step_size, ctx.white, ptr(g[0]),
+                                                               ptr(g[1]), ptr(g[2]), ptr(g_raw), ptr(t_shift),
+                                                               stream_of(rays)), "nerf_march_seg_composite_bwd")
+            return (g_raw,) + (None,) * 8
+        totals = ctx.saved_tensors[6]
+        # bytes: the above, and the cotangent of dist 4 B + the totals 16 B read per ray
+        with kernel_timer("march_seg_composite_bwd_dist", 56 * M + 68 * N, detail=True):
+            check(lib().nerf_march_seg_composite_bwd_dist(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
+                                                          ptr(out_step), ctx.step_size, ctx.white, ptr(g[0]),
+                                                          ptr(g[1]), ptr(g[2]), ptr(t_shift), ctx.inv_range,
+                                                          ptr(g[3]), ptr(totals), ptr(g_raw), stream_of(rays)),
+                  "nerf_march_seg_composite_bwd_dist")
+        return (g_raw,) + (None,) * 8
 
 
 def march_segments(rays: torch.Tensor, t_table: torch.Tensor, grid_u8: torch.Tensor, macro: Optional[torch.Tensor],
@@ -1101,7 +1129,7 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
                step_size: float = 0.005, t_thresh: float = 1e-4, bbox=SCENE_BBOX, white_bkgd: bool = True, dtype=F32,
                t_table: Optional[torch.Tensor] = None, k_schedule=(12, 24, 48, 96, 192, 384, 768),
                round_bytes: int = 1 << 31, use_macro: bool = True, max_points: Optional[int] = None,
-               t_shift: Optional[torch.Tensor] = None):
+               t_shift: Optional[torch.Tensor] = None, distortion: bool = False):
     """march() whose maps carry an autograd graph back to the packer's parameters: what the
     reference's render_accelerated gives when it is called with autograd on.  Two passes, in the
     spirit of the detached sample_pdf of render().  Pass A is march() itself, without gradient:
@@ -1122,7 +1150,14 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
     all), so that rays_kept >= 1 for N >= 1; the two numbers ride on pass A's host read.
 
     ``t_shift`` (float32 [N], ops.march_jitter): ray r's steps are t_table + t_shift[r] in both
-    passes, which read the same tensor (under a budget, its first rays_kept entries in pass B)."""
+    passes, which read the same tensor (under a budget, its first rays_kept entries in pass B).
+
+    ``distortion=True`` adds ``dist_map_f`` (float32 [N], carrying a graph): the distortion of each
+    ray's compositing weights on depths normalised by far - near (nerf_march_seg_composite_fwd_dist),
+    computed by pass B alone -- under ``max_points`` rows >= rays_kept are 0 with no graph.  The other
+    maps keep their bits."""
+    if distortion and not float(far) > float(near):
+        raise ValueError(f"march_grad: distortion needs far > near, got near {near}, far {far}")
     if max_points is not None:
         max_points = int(max_points)
         n_steps = (t_table.numel() if t_table is not None
@@ -1137,6 +1172,8 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
     used = out.pop("ray_used")
     seg_off = out.pop("seg_off", None)
     if walk is None:  # no rays
+        if distortion:
+            out["dist_map_f"] = torch.zeros(0, device=rays.device, dtype=torch.float32)
         return out
     rays_c, t_tab, _, g8, _, macro, vd = walk
     N = rays_c.shape[0]
@@ -1151,8 +1188,13 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
         t_shift = None if t_shift is None else t_shift[:n_keep]
     out_ray, out_step, out_pts = march_segments(rays_c, t_tab, g8, macro, seg_off, M, bbox, t_shift)
     raw = mlp(packer, out_pts, vd, 1, out_ray, dtype)
-    maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd),
-                                    t_shift)
+    if distortion:
+        maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd),
+                                        t_shift, 1.0 / (float(far) - float(near)))
+        out["dist_map_f"] = maps[3] if n_keep == N else torch.cat([maps[3], maps[3].new_zeros(N - n_keep)], 0)
+    else:
+        maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd),
+                                        t_shift)
     for k, v in zip(("rgb_map_f", "depth_map_f", "acc_map_f"), maps):
         out[k] = v if n_keep == N else torch.cat([v, out[k][n_keep:]], 0)  # (the dropped rows: pass A's, no graph)
     return out

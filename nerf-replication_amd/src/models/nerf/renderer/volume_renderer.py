@@ -14,6 +14,7 @@ Randomness (perturb > 0) comes from counter-based Philox streams inside the kern
 seeded from torch.initial_seed() and advanced per call (distribution-equivalent to the
 reference's torch.rand, not the same numbers).
 """
+import math
 import os
 import time
 
@@ -47,6 +48,17 @@ def march_jitter_setting(task_arg) -> bool:
     if not isinstance(v, bool):
         raise ValueError(f"task_arg.train_march_jitter must be true or false, got {v!r}")
     return v
+
+
+def distortion_loss_setting(task_arg) -> float:
+    """task_arg.distortion_loss_weight (float >= 0, default 0.0): the weight of the distortion of the rays'
+    weights in the loss of the training march (ops.march_grad(distortion=True)); 0 computes nothing."""
+    v = task_arg.get("distortion_loss_weight", 0.0)
+    if v is None:
+        return 0.0
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+        raise ValueError(f"task_arg.distortion_loss_weight must be a finite number >= 0, got {v!r}")
+    return float(v)
 
 
 class Renderer:
@@ -224,8 +236,12 @@ class Renderer:
         With task_arg.train_march_jitter every ray's steps are shifted by a random fraction of a step
         (ops.march_jitter): ONE draw for the whole batch, from this renderer's seed and call counter,
         before the split into chunks (a chunked step equals the unchunked one), returned as t_shift.
-        Only this path jitters: the no-grad march of render_accelerated never does."""
+        Only this path jitters: the no-grad march of render_accelerated never does.
+        With task_arg.distortion_loss_weight > 0 the result also has dist_map_f (the distortion of each
+        ray's weights, with a graph), concatenated over the chunks like the other maps; the no-grad
+        march never computes it."""
         ta = cfg.task_arg
+        distortion = distortion_loss_setting(ta) > 0.0
         start = time.time()
         chunk = self._chunk(True)
         packer = self.net.model_fine.packer()
@@ -239,21 +255,25 @@ class Renderer:
             out = ops.march_grad(packer, rays_flat, near, far, self.occupancy_grid,
                                  step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
                                  bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
-                                 k_schedule=sched, max_points=int(self.max_points), t_shift=t_shift)
+                                 k_schedule=sched, max_points=int(self.max_points), t_shift=t_shift,
+                                 distortion=distortion)
             keys = ("rgb_map_f", "depth_map_f", "acc_map_f", "n_queried", "n_evaluated", "rounds", "rays_kept",
-                    "n_points")
+                    "n_points") + (("dist_map_f",) if distortion else ())
             ret = {k: out[k] for k in keys}
             ret["render_time"] = time.time() - start
             if t_shift is not None:
                 ret["t_shift"] = t_shift
             return ret
         maps = {"rgb_map_f": [], "depth_map_f": [], "acc_map_f": []}
+        if distortion:
+            maps["dist_map_f"] = []
         counts = {"n_queried": 0, "n_evaluated": 0, "rounds": 0}
         for i in range(0, rays_flat.shape[0], chunk):
             out = ops.march_grad(packer, rays_flat[i:i + chunk], near, far, self.occupancy_grid,
                                  step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
                                  bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
-                                 k_schedule=sched, t_shift=None if t_shift is None else t_shift[i:i + chunk])
+                                 k_schedule=sched, t_shift=None if t_shift is None else t_shift[i:i + chunk],
+                                 distortion=distortion)
             for k, v in maps.items():
                 v.append(out[k])
             for k in counts:

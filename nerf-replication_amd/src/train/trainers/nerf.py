@@ -37,6 +37,13 @@ different ray counts (each rank weighs 1 / world, not its rays); the online grid
 step in each training forward (Renderer._render_accelerated_grad; ret["t_shift"]).  Validation and every
 other no-grad march keep the fixed steps.  The renderer's seed contains the rank, so ranks draw different
 shifts; the stream restarts with the renderer's call counter on resume, as the ``perturb`` stream does.
+
+``task_arg.distortion_loss_weight: W`` (float >= 0, default 0.0; positive only with ``train_renderer:
+accelerated``, either ``train_grid``, with or without a point budget or jitter) adds Mip-NeRF 360's
+distortion of each ray's compositing weights to the training loss: loss = MSE + W * mean(dist_map_f),
+the mean over the rays the MSE runs over (the first ``rays_kept`` under a point budget), stats gain
+``loss_dist`` (the unweighted mean).  Per rank, like the MSE: no collective.  Exactly 0 computes nothing:
+every launch, output and stats key is what it was.  Validation never computes it.
 """
 import os
 
@@ -48,7 +55,7 @@ from nerf_amd import ops
 from src.config import cfg
 from src.models.nerf.renderer.online_grid import OnlineGrid, grid_update_settings
 from src.models.nerf.renderer.ray_budget import RayBudget
-from src.models.nerf.renderer.volume_renderer import Renderer, march_jitter_setting
+from src.models.nerf.renderer.volume_renderer import Renderer, distortion_loss_setting, march_jitter_setting
 
 TRAIN_RENDERERS = ("hierarchical", "accelerated")
 TRAIN_GRIDS = ("file", "online")
@@ -80,6 +87,10 @@ class NetworkWrapper(nn.Module):
         if self.march_jitter and self.train_renderer != "accelerated":
             raise ValueError("task_arg.train_march_jitter: true jitters the steps of train_renderer: accelerated; "
                              f"with train_renderer: {self.train_renderer} the samples follow task_arg.perturb")
+        self.distortion_weight = distortion_loss_setting(cfg.task_arg)
+        if self.distortion_weight > 0.0 and self.train_renderer != "accelerated":
+            raise ValueError("task_arg.distortion_loss_weight > 0 regularises the weights of train_renderer: "
+                             f"accelerated; with train_renderer: {self.train_renderer} there is no such term")
         self.ray_budget = RayBudget.from_config(cfg.task_arg)  # (None: point_budget.target 0, the fixed train_rays)
         if self.ray_budget is not None:
             self.renderer.max_points = self.ray_budget.max_points
@@ -143,17 +154,29 @@ class NetworkWrapper(nn.Module):
         if self.train_loader is not None:
             self.train_loader.dataset.batch_rays = self.ray_budget.rays
 
+    def _march_loss(self, ret, gt, kept=None):
+        """MSE(rgb_map_f, gt) over the first ``kept`` rays (all of them when None), plus the weighted mean
+        distortion when the renderer returned the map -> (total, stats)."""
+        rgb, gt = (ret["rgb_map_f"], gt) if kept is None else (ret["rgb_map_f"][:kept], gt[:kept])
+        loss_f, _, total = ops.mse_pair(rgb, None, gt)
+        if "dist_map_f" not in ret:
+            return total, {"loss_f": loss_f, "total_loss": total}
+        dist = ret["dist_map_f"] if kept is None else ret["dist_map_f"][:kept]
+        loss_dist = dist.mean()
+        total = total + self.distortion_weight * loss_dist
+        return total, {"loss_f": loss_f, "loss_dist": loss_dist.detach(), "total_loss": total}
+
     def _budgeted_step(self, batch, gt):
         """The training forward under a point budget: one capped march, the loss over the kept rays, then the
         observation of ALL marched rays (the dropped ones were marched too) that sets the next count."""
         ret = self.renderer.render_accelerated(batch)
         kept, n = ret["rays_kept"], ret["rgb_map_f"].shape[0]
-        loss_f, _, total = ops.mse_pair(ret["rgb_map_f"][:kept], None, gt[:kept])
+        total, stats = self._march_loss(ret, gt, kept)
         self.ray_budget.observe(n, ret["n_queried"])
         self._publish_rays()
         # (host tensors: a device scalar per step would be a blocking pageable copy, ops.device_scalar)
-        return ret, total, {"loss_f": loss_f, "total_loss": total, "rays": torch.tensor(float(n)),
-                            "points": torch.tensor(float(ret["n_points"]))}
+        stats.update(rays=torch.tensor(float(n)), points=torch.tensor(float(ret["n_points"])))
+        return ret, total, stats
 
     def forward(self, batch):
         gt = batch["rgbs"].reshape(-1, 3) if batch["rgbs"].dim() == 3 else batch["rgbs"]
@@ -168,16 +191,16 @@ class NetworkWrapper(nn.Module):
             if budgeted:
                 return self._budgeted_step(batch, gt)
             ret = self.renderer.render_accelerated(batch)
-            loss_f, _, total = ops.mse_pair(ret["rgb_map_f"], None, gt)
-            return ret, total, {"loss_f": loss_f, "total_loss": total}
+            total, stats = self._march_loss(ret, gt)
+            return ret, total, stats
         if budgeted:
             return self._budgeted_step(batch, gt)
         if self.train_renderer == "accelerated" and torch.is_grad_enabled():
             # the fine net through the grid march; the MSE and its backward in one launch each
             # (ops.mse_pair with no second image)
             ret = self.renderer.render_accelerated(batch)
-            loss_f, _, total = ops.mse_pair(ret["rgb_map_f"], None, gt)
-            return ret, total, {"loss_f": loss_f, "total_loss": total}
+            total, stats = self._march_loss(ret, gt)
+            return ret, total, stats
         ret = self.renderer.render(batch)
         if "rgb_map_f" in ret and ret["rgb_map_c"].is_cuda and cfg.task_arg.get("fuse_mse", True):
             # both MSEs and their sum in one launch, the backward in one (ops.mse_pair)

@@ -3,6 +3,7 @@ from-scratch run through the march converges against the hierarchical one.
 
     python tools/grid_train_bench.py [--tiers fp32,bf16x3f] [--out profiles/r8/online_grid.json]
     python tools/grid_train_bench.py --jitter [--out profiles/r10/march_jitter.json]
+    python tools/grid_train_bench.py --distortion 0.001,0.01 [--out profiles/r11/distortion.json]
 
 One process, HIP events on the compute stream, medians.
 
@@ -20,6 +21,8 @@ convergence the procedural scene (src/datasets/nerf/synthetic.py), seed-0 init, 
             the wall-clock spent in training steps (evaluation excluded), per tier.
 --jitter    the convergence part alone, online-accelerated with task_arg.train_march_jitter off and on
             (same scene, seed, ray stream, steps and tiers), merged into --out under "convergence".
+--distortion W[,W...]  the convergence part alone, online-accelerated with task_arg.distortion_loss_weight 0 and
+            each W (same scene, seed, ray stream, steps and tiers), merged into --out under "convergence".
 """
 import argparse
 import json
@@ -62,10 +65,20 @@ def main():
     ap.add_argument("--rays", type=int, default=4096, help="convergence: rays per step")
     ap.add_argument("--jitter", action="store_true",
                     help="convergence only: online-accelerated with train_march_jitter off and on")
+    ap.add_argument("--distortion", default=None, metavar="W[,W...]",
+                    help="convergence only: online-accelerated with distortion_loss_weight 0 and each W")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    dist_weights = [float(w) for w in a.distortion.split(",")] if a.distortion else []
+    if a.jitter and dist_weights:
+        ap.error("--jitter and --distortion are separate runs")
+    if any(not w > 0 for w in dist_weights):
+        ap.error("--distortion takes positive weights (the run with the weight 0 is always made)")
+    conv_only = a.jitter or bool(dist_weights)
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", *(("r10", "march_jitter.json") if a.jitter else ("r8", "online_grid.json")))
+        a.out = os.path.join(ROOT, "profiles", *(("r10", "march_jitter.json") if a.jitter else
+                                                 ("r11", "distortion.json") if dist_weights else
+                                                 ("r8", "online_grid.json")))
     from nerf_amd import ops
     from src.config import cfg
     from src.datasets.nerf.blender import Dataset
@@ -109,7 +122,7 @@ def main():
 
     # ---- update cost ---------------------------------------------------------------------------------
     ta.perturb = 0
-    for dtype in () if a.jitter else a.tiers.split(","):
+    for dtype in () if conv_only else a.tiers.split(","):
         packer = fixture_net(dtype).model_fine.packer()
         g = OnlineGrid(128, float(ta.occupancy_grid_threshold), bbox, dev, **DEFAULTS)
         for _ in range(2):
@@ -126,7 +139,7 @@ def main():
         print("update", dtype, json.dumps(result["update"][dtype]), flush=True)
 
     # ---- the step, online (amortised) against file mode ----------------------------------------------
-    for dtype in () if a.jitter else a.tiers.split(","):
+    for dtype in () if conv_only else a.tiers.split(","):
         ta.mlp_dtype = dtype
         stacks = {}
         for mode in ("file", "online"):
@@ -183,10 +196,13 @@ def main():
         result["convergence"][dtype] = {"rays_per_step": a.rays, "steps": a.steps, "all_white_psnr_db": round(white_db, 3)}
         modes = ("online_accelerated", "online_accelerated_jitter") if a.jitter else ("online_accelerated",
                                                                                       "hierarchical")
+        if dist_weights:
+            modes = ("online_accelerated",) + tuple(f"online_accelerated_distortion_{w:g}" for w in dist_weights)
         for mode in modes:
             ta.mlp_dtype = dtype
             ta.perturb = 1
             ta.train_march_jitter = mode == "online_accelerated_jitter"
+            ta.distortion_loss_weight = float(mode.rsplit("_", 1)[1]) if "_distortion_" in mode else 0.0
             ta.train_renderer, ta.train_grid = ("accelerated", "online") if mode != "hierarchical" else ("hierarchical",
                                                                                                          "file")
             torch.manual_seed(0)
@@ -230,9 +246,10 @@ def main():
             torch.cuda.empty_cache()
     reset_modes()
     ta.train_march_jitter = False
+    ta.distortion_loss_weight = 0.0
 
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    if a.jitter:  # the jitter file also holds the cost measurements of other tools: only this part is replaced
+    if conv_only:  # the file also holds the cost measurements of other tools: only this part is replaced
         conv = result["convergence"]
         result = json.load(open(a.out)) if os.path.exists(a.out) else {}
         result.update(device=torch.cuda.get_device_name(0), convergence=conv)
