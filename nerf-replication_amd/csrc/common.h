@@ -91,6 +91,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // torch.sum(x, -1) of one contiguous fp32 row on the CPU, bit for bit, for n <= 64 values held
 // one per lane (x_i on lane i, any value beyond n).  sample_pdf normalises by this sum
@@ -134,24 +139,21 @@ __device__ __forceinline__ double wave_scan_mul(double v) {
   }
   return v;
 }
-__device__ __forceinline__ double wave_scan_add(double v) {
+// inclusive sum scan across the wave, one body for the four types it is used at
+template <class T>
+__device__ __forceinline__ T wave_scan_add_t(T v) {
   int l = lane_id();
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    double t = __shfl_up(v, o, 64);
+    T t = __shfl_up(v, o, 64);
     if (l >= o) v += t;
   }
   return v;
 }
-__device__ __forceinline__ float wave_scan_add_f(float v) {
-  int l = lane_id();
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    float t = __shfl_up(v, o, 64);
-    if (l >= o) v += t;
-  }
-  return v;
-}
+__device__ __forceinline__ double wave_scan_add(double v) { return wave_scan_add_t(v); }
+__device__ __forceinline__ float wave_scan_add_f(float v) { return wave_scan_add_t(v); }
+__device__ __forceinline__ int wave_scan_add_i(int v) { return wave_scan_add_t(v); }
+__device__ __forceinline__ long long wave_scan_add_i64(long long v) { return wave_scan_add_t(v); }
 
 }  // namespace nerf
 #endif

@@ -913,17 +913,19 @@ def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: 
     rounds (ray_used.sum() == n_queried); the other outputs are the same bit for bit.  ``t_shift``
     (float32 [N], ops.march_jitter) moves ray r's steps to t_table + t_shift[r] (one rounded fp32
     add per step, the skip still exact); None is the table as it is, with the same launches."""
-    return _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table, k_schedule,
-                  round_bytes, k_low, t_split, sync_every, use_macro, one_pass, k_low_grow, return_used,
-                  t_shift=t_shift)[0]
+    return _march(packer, rays, near, far, grid, step_size=step_size, t_thresh=t_thresh, bbox=bbox,
+                  white_bkgd=white_bkgd, dtype=dtype, t_table=t_table, k_schedule=k_schedule, round_bytes=round_bytes,
+                  k_low=k_low, t_split=t_split, sync_every=sync_every, use_macro=use_macro, one_pass=one_pass,
+                  k_low_grow=k_low_grow, return_used=return_used, t_shift=t_shift)[0]
 
 
-def _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table, k_schedule,
-           round_bytes, k_low, t_split, sync_every, use_macro, one_pass, k_low_grow, return_used, budget=None,
-           t_shift=None):
+def _march(packer, rays, near, far, grid, *, step_size, t_thresh, bbox, white_bkgd, dtype, t_table, k_schedule,
+           round_bytes, use_macro, k_low=8, t_split=0.9, sync_every=4, one_pass=True, k_low_grow=8,
+           return_used=False, budget=None, t_shift=None):
     """march() -> (its result, the walk's inputs for a second pass over the same rays: the
     contiguous rays, the t table, the uint8 grid, its macro blocks, the unit view directions).
-    With ``budget`` (needs return_used) the per-ray counts are also cut at that many points
+    The options are march()'s, by keyword; the ones with a default here are those march_grad leaves
+    alone.  With ``budget`` (needs return_used) the per-ray counts are also cut at that many points
     (nerf_march_budget, enqueued before the march's one host read, whose spare slots carry its two
     numbers: no further synchronisation): the result gains seg_off (int32 [N+1]), rays_kept, n_points."""
     rays = _f32c(rays.reshape(-1, 6), "rays")
@@ -1038,24 +1040,22 @@ class _MarchSegComposite(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.step_size, ctx.white = float(step_size), int(bool(white))
         ctx.inv_range = None if inv_range is None else float(inv_range)
+        # (what the plain and the dist entry point both begin with)
+        head = (ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step), ctx.step_size, ctx.white,
+                ptr(rgb), ptr(depth), ptr(acc), ptr(t_shift))
         if inv_range is None:
             # bytes: raw 16 B + step 4 B per point; ray 24 B, offsets 4 B, rgb/depth/acc 20 B per ray
             with kernel_timer("march_seg_composite_fwd", 20 * M + 48 * N, detail=True):
-                check(lib().nerf_march_seg_composite_fwd_shift(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
-                                                               ptr(out_step), float(step_size), int(bool(white)),
-                                                               ptr(rgb), ptr(depth), ptr(acc), ptr(t_shift),
-                                                               stream_of(rays)), "nerf_march_seg_composite_fwd")
+                check(lib().nerf_march_seg_composite_fwd_shift(*head, stream_of(rays)),
+                      "nerf_march_seg_composite_fwd")
             ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift)
             return rgb, depth, acc
         dist = torch.empty(N, device=dev, dtype=torch.float32)
         totals = torch.empty(N, 2, device=dev, dtype=torch.float64)
         # bytes: the above, and dist 4 B + the totals 16 B written per ray
         with kernel_timer("march_seg_composite_fwd_dist", 20 * M + 68 * N, detail=True):
-            check(lib().nerf_march_seg_composite_fwd_dist(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
-                                                          ptr(out_step), float(step_size), int(bool(white)),
-                                                          ptr(rgb), ptr(depth), ptr(acc), ptr(t_shift),
-                                                          ctx.inv_range, ptr(dist), ptr(totals), stream_of(rays)),
-                  "nerf_march_seg_composite_fwd_dist")
+            check(lib().nerf_march_seg_composite_fwd_dist(*head, ctx.inv_range, ptr(dist), ptr(totals),
+                                                          stream_of(rays)), "nerf_march_seg_composite_fwd_dist")
         ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift, totals)
         return rgb, depth, acc, dist
 
@@ -1067,21 +1067,19 @@ class _MarchSegComposite(torch.autograd.Function):
         N, M = rays.shape[0], raw.shape[0]
         g = [None if t is None else _f32c(t, "cotangent") for t in grads]
         g_raw = torch.empty_like(raw)
+        head = (ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step), ctx.step_size, ctx.white,
+                ptr(g[0]), ptr(g[1]), ptr(g[2]))
         if ctx.inv_range is None:
             # bytes: raw 16 B + step 4 B read twice (entry transmittances, then the reverse walk), d_raw 16 B written
             with kernel_timer("march_seg_composite_bwd", 56 * M + 48 * N, detail=True):
-                check(lib().nerf_march_seg_composite_bwd_shift(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
-                                                               ptr(out_step), ctx.step_size, ctx.white, ptr(g[0]),
-                                                               ptr(g[1]), ptr(g[2]), ptr(g_raw), ptr(t_shift),
-                                                               stream_of(rays)), "nerf_march_seg_composite_bwd")
+                check(lib().nerf_march_seg_composite_bwd_shift(*head, ptr(g_raw), ptr(t_shift), stream_of(rays)),
+                      "nerf_march_seg_composite_bwd")
             return (g_raw,) + (None,) * 8
         totals = ctx.saved_tensors[6]
         # bytes: the above, and the cotangent of dist 4 B + the totals 16 B read per ray
         with kernel_timer("march_seg_composite_bwd_dist", 56 * M + 68 * N, detail=True):
-            check(lib().nerf_march_seg_composite_bwd_dist(ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off),
-                                                          ptr(out_step), ctx.step_size, ctx.white, ptr(g[0]),
-                                                          ptr(g[1]), ptr(g[2]), ptr(t_shift), ctx.inv_range,
-                                                          ptr(g[3]), ptr(totals), ptr(g_raw), stream_of(rays)),
+            check(lib().nerf_march_seg_composite_bwd_dist(*head, ptr(t_shift), ctx.inv_range, ptr(g[3]),
+                                                          ptr(totals), ptr(g_raw), stream_of(rays)),
                   "nerf_march_seg_composite_bwd_dist")
         return (g_raw,) + (None,) * 8
 
@@ -1166,8 +1164,9 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
             raise ValueError(f"march_grad: max_points must be in [{n_steps} (the march's steps: one ray can need "
                              f"them all), 2^31 - 1], got {max_points}")
     with torch.no_grad():
-        out, walk = _march(packer, rays, near, far, grid, step_size, t_thresh, bbox, white_bkgd, dtype, t_table,
-                           k_schedule, round_bytes, 8, 0.9, 4, use_macro, True, 8, True, max_points,
+        out, walk = _march(packer, rays, near, far, grid, step_size=step_size, t_thresh=t_thresh, bbox=bbox,
+                           white_bkgd=white_bkgd, dtype=dtype, t_table=t_table, k_schedule=k_schedule,
+                           round_bytes=round_bytes, use_macro=use_macro, return_used=True, budget=max_points,
                            t_shift=t_shift)
     used = out.pop("ray_used")
     seg_off = out.pop("seg_off", None)

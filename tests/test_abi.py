@@ -38,6 +38,46 @@ def test_every_declared_symbol_is_exported(lib):
         assert name in _lib.SIGNATURES, f"{name} has no ctypes signature"
 
 
+def declared_prototypes():
+    """name -> (return type, [parameter types]) of every prototype in the header, as C text
+    without the parameter names."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(nerf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        params = [p.strip() for p in params.split(",")]
+        if params == ["void"] or params == [""]:
+            params = []
+        # drop the parameter's name: what is left of the last identifier, stars kept with the type
+        protos[name] = (" ".join(ret.split()), [re.sub(r"\s*\b\w+$", "", p).replace(" *", "*") for p in params])
+    return protos
+
+
+def test_ctypes_signatures_match_the_header():
+    """Every prototype of include/nerf_amd.h against _lib.SIGNATURES: the return type, the
+    parameter count and each parameter's class (pointer or hipStream_t -> c_void_p, int -> c_int,
+    int64_t -> c_int64, uint64_t -> c_uint64, float -> c_float, double -> c_double).  A wrong
+    entry would pass garbage to a kernel without any error; nothing is launched here."""
+    import ctypes
+    from nerf_amd import _lib
+    scalars = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+               "double": ctypes.c_double, "hipStream_t": ctypes.c_void_p}
+
+    def ctype_of(c_type, ret=False):
+        if c_type.endswith("*"):
+            return ctypes.c_char_p if ret and c_type == "const char*" else ctypes.c_void_p
+        return scalars[c_type]  # (KeyError: a C type this test does not know yet)
+
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_functions() == sorted(_lib.SIGNATURES)
+    for name, (ret, params) in protos.items():
+        res, args = _lib.SIGNATURES[name]
+        assert res is ctype_of(ret, ret=True), f"{name}: returns {ret}, bound as {res}"
+        assert len(args) == len(params), f"{name}: {len(params)} parameters declared, {len(args)} bound"
+        for i, (p, got) in enumerate(zip(params, args)):
+            assert got is ctype_of(p), f"{name}: parameter {i} is {p}, bound as {got}"
+
+
 def test_sizes_and_layout(lib):
     assert lib.nerf_abi_version() == 4
     assert lib.nerf_mlp_net_params() == 595844

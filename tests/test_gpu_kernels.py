@@ -585,13 +585,13 @@ MARCH_CASES += [(d, r, True, True, False, 24.0) for d in (0.3, "blob") for r in 
 
 @pytest.mark.parametrize("density,res,macro,one_pass,tight,far", MARCH_CASES)
 def test_march_gather_empty_cell_skip_exact(cuda, ops, density, res, macro, one_pass, tight, far):
-    """The march gather skips the steps that provably stay in an empty cell (grid.hip,
+    """The march gather skips the steps that provably stay in an empty cell (march.hip,
     march_skip_empty).  Against brute force -- the occupancy of EVERY step's point o + t d
     (volume_renderer.py:298-309: clamp, normalise, x127, truncate) -- the one-round gather with
     K = all steps emits exactly the occupied (ray, step) pairs, in step order: rays from outside
     the box and from inside, axis-aligned direction components (d = 0), sparse and dense grids,
     at the config's res 128 and at 512 / 1024 (where 1e-3 of a cell alone would approach the fp32
-    error of the points; grid.hip's margin has an absolute floor), with and without the macro
+    error of the points; march.hip's margin has an absolute floor), with and without the macro
     grid (whole empty 8^3 blocks crossed in one skip; 'blob' = an object in empty space).  The
     one-pass form writes the points from the runs its counting walk recorded (16 per lane, then
     the walk again: the dense grids' rays have far more runs) and must equal the two-pass form;

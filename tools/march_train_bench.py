@@ -1,6 +1,6 @@
 """The training step through the occupancy-grid march against the hierarchical one.
 
-    python tools/march_train_bench.py [--steps 24] [--warmup 5] [--out profiles/r7/march_train.json]
+    python tools/march_train_bench.py [--steps 24] [--warmup 5] [--out profiles/r7/march_train.json] [--lib PATH]
 
 One process, the trained fixture net (tests/golden/trained_v2.npz) and its res-128 bake, the
 golden_v2 ``rays4096`` batch.  For each MLP tier (fp32, bf16x3, bf16x3f, bf16) it times
@@ -48,7 +48,11 @@ def main():
     ap.add_argument("--split-reps", type=int, default=10)
     ap.add_argument("--tiers", default=",".join(TIERS))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r7", "march_train.json"))
+    ap.add_argument("--lib", default=None, help="alternative build of libnerf_amd.so")
     a = ap.parse_args()
+    from nerf_amd import _lib
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     from nerf_amd import ops
     from src.config import cfg
     from src.models.nerf.network import Network
@@ -134,9 +138,9 @@ def main():
             opt.zero_grad()
             ev[0].record()
             with torch.no_grad():
-                out, walk = ops._march(packer, rays, 2.0, 6.0, r.occupancy_grid, kw["step_size"], kw["t_thresh"],
-                                       kw["bbox"], kw["white_bkgd"], dtype, None, TRAIN_K_SCHEDULE, 1 << 31, 8,
-                                       0.9, 4, True, True, 8, True)
+                out, walk = ops._march(packer, rays, 2.0, 6.0, r.occupancy_grid, t_table=None,
+                                       k_schedule=TRAIN_K_SCHEDULE, round_bytes=1 << 31, use_macro=True,
+                                       return_used=True, **kw)
             ev[1].record()
             rays_c, t_tab, _, g8, _, macro, vd = walk
             seg_off = torch.zeros(rays_c.shape[0] + 1, dtype=torch.int32, device=dev)
