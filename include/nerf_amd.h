@@ -51,6 +51,17 @@ int nerf_abi_version(void);
 int nerf_raygen(const float* c2w, int n_img, int H, int W, float focal, const int64_t* pix, int64_t R,
                 uint64_t seed, uint64_t offset, const float* images, float* rays, float* rgb, int64_t* pix_out,
                 hipStream_t stream);
+/* The same rays and pixel ids (bit for bit, for the same seed / offset / pix) from straight-alpha pixels
+ * images_rgba [n_img,H,W,4] (fp32, 16-byte aligned), composited onto a colour per ray:
+ *   rgb[r,c] = fadd(fmul(C_c, a), fmul(fsub(1, a), bg[r,c]))   (each op rounded on its own)
+ * bg[r] = bg_in[r] (nullable [R,3]), else three Philox-4x32-10 uniforms (x >> 8) * 2^-24: words x, y, z
+ * of one call with the pixel draw's key and the counter (r lo, r hi, offset lo, offset hi | 0x80000000).
+ * offset must be < 2^63 (-22), so the colour stream is disjoint from the pixel-id stream.  bg_out
+ * (nullable [R,3]) receives the colours.  R == 0 is a no-op; a null c2w / images_rgba / rays / rgb with
+ * R > 0 is -22 before any launch.  (Added within ABI 4.) */
+int nerf_raygen_rgba(const float* c2w, int n_img, int H, int W, float focal, const int64_t* pix, int64_t R,
+                     uint64_t seed, uint64_t offset, const float* images_rgba, const float* bg_in, float* rays,
+                     float* rgb, int64_t* pix_out, float* bg_out, hipStream_t stream);
 
 /* ---- (a3) stratified depths --------------------------------------------------------------
  * Replaces Renderer.render :165-187 (linspace, perturb, pts = o + d z, viewdirs = d/|d|).
@@ -329,6 +340,25 @@ int nerf_march_seg_composite_bwd_dist(const float* raw, const float* rays, int64
                                       const float* g_rgb, const float* g_depth, const float* g_acc,
                                       const float* t_shift, float inv_range, const float* g_dist,
                                       const double* totals, float* g_raw, hipStream_t stream);
+
+/* ---- (a14) a background colour per ray (training through the grid on RGBA views) -----------------------
+ * The _dist pair's signatures plus bg [N,3] (fp32, before the stream).  A non-null bg overrides `white`:
+ *   rgb[r,c] = sum_k w_k c_k + fmul(fsub(1, acc[r]), bg[r,c])        (depth, acc, dist untouched)
+ *   g_acc'   = g_acc - (g_r bg_0 + g_g bg_1 + g_b bg_2)              (double, summed in that order)
+ * bg is a constant of the step: it gets no gradient.  bg = 1 gives the bits of white = 1, bg = 0 those of
+ * white = 0.  dist == NULL (forward) / totals == NULL (backward) selects the kernels without the
+ * distortion term; inv_range is not checked then.  bg == NULL forwards to the entry points above (their
+ * bits).  The kernels are the BG instantiations of the same templates: no atomics, no workspace, no
+ * allocation, no host sync, a fixed summation order.  (Added within ABI 4.) */
+int nerf_march_seg_composite_fwd_bg(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                    const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                    float* rgb, float* depth, float* acc, const float* t_shift, float inv_range,
+                                    float* dist, double* totals, const float* bg, hipStream_t stream);
+int nerf_march_seg_composite_bwd_bg(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                    const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                    const float* g_rgb, const float* g_depth, const float* g_acc,
+                                    const float* t_shift, float inv_range, const float* g_dist,
+                                    const double* totals, float* g_raw, const float* bg, hipStream_t stream);
 
 /* ---- (a12) point budget: pass A's counts -> pass B's segments, cut at a budget of points ---------------
  * ray_used[N] (int32, >= 0) -> seg_off[N+1] (int32) and keep[2] (int64, device):

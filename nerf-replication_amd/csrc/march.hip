@@ -519,6 +519,8 @@ struct SegCompArgs {
   double* totals = nullptr;         // [N,2] forward output: the ray's (sum w, sum w t)
   const float* g_dist = nullptr;    // [N] backward input (nullable = 0)
   const double* totals_in = nullptr;  // [N,2] backward input: what the forward wrote
+  // the per-ray background colour (the BG instantiations alone read it)
+  const float* bg = nullptr;  // [N,3]
 };
 
 constexpr int SEG_WAVES = 4;  // rays (waves) per 256-thread block
@@ -557,7 +559,10 @@ __device__ __forceinline__ float seg_sigmoid(float x) { return 1.f / (1.f + expf
 // Wex_i = sum_{j<i} w_j, Sex_i = sum_{j<i} w_j t_j: two more add scans across the lanes per chunk, in
 // double, their totals carried from chunk to chunk like T_in.  The ray's totals (W, S) go out for the
 // backward.  DIST is a template parameter like SHIFT: without it the kernel is the code it was.
-template <bool SHIFT, bool DIST>
+//
+// BG composites onto the ray's own colour bg[r] instead of white: rgb += (1 - acc) * bg[r], whatever
+// `white` says.  A third template parameter, for the same reason.
+template <bool SHIFT, bool DIST, bool BG>
 __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompArgs a) {
   const int64_t r = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
   if (r >= a.N) return;  // (wave-uniform)
@@ -605,10 +610,17 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompAr
   sa = wave_sum_d(sa);
   if (l == 0) {
     const float acc = (float)sa;
-    const float bg = a.white ? fsub(1.f, acc) : 0.f;  // rgb += (1 - acc) * 1
-    a.rgb[r * 3 + 0] = fadd((float)sr, bg);
-    a.rgb[r * 3 + 1] = fadd((float)sg, bg);
-    a.rgb[r * 3 + 2] = fadd((float)sb, bg);
+    if constexpr (BG) {
+      const float left = fsub(1.f, acc);  // rgb += (1 - acc) * bg[r]
+      a.rgb[r * 3 + 0] = fadd((float)sr, fmul(left, a.bg[r * 3 + 0]));
+      a.rgb[r * 3 + 1] = fadd((float)sg, fmul(left, a.bg[r * 3 + 1]));
+      a.rgb[r * 3 + 2] = fadd((float)sb, fmul(left, a.bg[r * 3 + 2]));
+    } else {
+      const float bg = a.white ? fsub(1.f, acc) : 0.f;  // rgb += (1 - acc) * 1
+      a.rgb[r * 3 + 0] = fadd((float)sr, bg);
+      a.rgb[r * 3 + 1] = fadd((float)sg, bg);
+      a.rgb[r * 3 + 2] = fadd((float)sb, bg);
+    }
     a.depth[r] = (float)sd;
     a.acc[r] = acc;
   }
@@ -637,7 +649,9 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_fwd_kernel(SegCompAr
 // suffix sums of w and w t over the chunks behind it next to C; within a chunk two add scans across the
 // lanes give the rest, and a point's exclusive prefix is the forward's saved total minus its inclusive
 // suffix, all in double.  No second pre-pass, no state per chunk.
-template <bool SHIFT, bool DIST>
+//
+// BG: g_acc' = g_acc - g_rgb . bg[r] (the colour is a constant of the step: no gradient of its own).
+template <bool SHIFT, bool DIST, bool BG>
 __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_bwd_kernel(SegCompArgs a) {
   const int64_t r = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
   if (r >= a.N) return;  // (wave-uniform)
@@ -649,7 +663,12 @@ __global__ void __launch_bounds__(64 * SEG_WAVES) march_seg_bwd_kernel(SegCompAr
   const double gr = a.g_rgb ? (double)a.g_rgb[r * 3 + 0] : 0.0, gg = a.g_rgb ? (double)a.g_rgb[r * 3 + 1] : 0.0,
                gb = a.g_rgb ? (double)a.g_rgb[r * 3 + 2] : 0.0;
   const double gd = a.g_depth ? (double)a.g_depth[r] : 0.0;
-  const double ga = (a.g_acc ? (double)a.g_acc[r] : 0.0) - (a.white ? gr + gg + gb : 0.0);
+  double gbg;  // g_rgb . background
+  if constexpr (BG)
+    gbg = gr * (double)a.bg[r * 3 + 0] + gg * (double)a.bg[r * 3 + 1] + gb * (double)a.bg[r * 3 + 2];
+  else
+    gbg = a.white ? gr + gg + gb : 0.0;
+  const double ga = (a.g_acc ? (double)a.g_acc[r] : 0.0) - gbg;
   const int64_t nchunks = (end - beg + 63) / 64, nsuper = (nchunks + 63) / 64;
   double chunkT = 1.0, superT = 1.0;
   {
@@ -962,8 +981,8 @@ int nerf_march_segments(const float* rays, int64_t N, const float* t_table, int 
                                    out_pts, nullptr, stream);
 }
 
-// The four segment compositors (forward / backward, plain / with the distortion term) check and
-// launch here.  `name` is the entry point's: it heads every message.  `a` holds what the entry point
+// The segment compositors (forward / backward, plain / with the distortion term, white / a colour
+// per ray) check and launch here.  `name` is the entry point's: it heads every message.  `a` holds what the entry point
 // was given, null elsewhere.
 static int seg_composite(const char* name, bool bwd, bool dist, const SegCompArgs& a, hipStream_t stream) {
   NERF_REQUIRE(a.N >= 0, "%s: N must be >= 0", name);
@@ -978,9 +997,11 @@ static int seg_composite(const char* name, bool bwd, bool dist, const SegCompArg
   const dim3 grid((unsigned)((a.N + SEG_WAVES - 1) / SEG_WAVES)), block(64 * SEG_WAVES);
   pick(a.t_shift != nullptr, [&](auto S) {
     pick(dist, [&](auto D) {
-      constexpr bool s = decltype(S)::value, d = decltype(D)::value;
-      if (bwd) hipLaunchKernelGGL((march_seg_bwd_kernel<s, d>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((march_seg_fwd_kernel<s, d>), grid, block, 0, stream, a);
+      pick(a.bg != nullptr, [&](auto B) {
+        constexpr bool s = decltype(S)::value, d = decltype(D)::value, b = decltype(B)::value;
+        if (bwd) hipLaunchKernelGGL((march_seg_bwd_kernel<s, d, b>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((march_seg_fwd_kernel<s, d, b>), grid, block, 0, stream, a);
+      });
     });
   });
   return check_launch(name);
@@ -1040,6 +1061,45 @@ int nerf_march_seg_composite_bwd_dist(const float* raw, const float* rays, int64
   a.g_rgb = g_rgb, a.g_depth = g_depth, a.g_acc = g_acc, a.g_raw = g_raw, a.t_shift = t_shift;
   a.inv_range = inv_range, a.g_dist = g_dist, a.totals_in = totals;
   return seg_composite("nerf_march_seg_composite_bwd_dist", true, true, a, stream);
+}
+
+// The same pair on a background colour per ray, bg [N,3] (the BG instantiations): rgb += (1 - acc) bg[r]
+// whatever `white` says, g_acc' = g_acc - g_rgb . bg[r].  A null dist (forward) or totals (backward)
+// selects the kernels without the distortion term (inv_range is not read then); a null bg is the
+// entry point above, or the _shift one.
+int nerf_march_seg_composite_fwd_bg(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                    const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                    float* rgb, float* depth, float* acc, const float* t_shift, float inv_range,
+                                    float* dist, double* totals, const float* bg, hipStream_t stream) {
+  if (!bg) {
+    if (dist)
+      return nerf_march_seg_composite_fwd_dist(raw, rays, N, t_table, seg_off, out_step, step_size, white, rgb, depth,
+                                               acc, t_shift, inv_range, dist, totals, stream);
+    return nerf_march_seg_composite_fwd_shift(raw, rays, N, t_table, seg_off, out_step, step_size, white, rgb, depth,
+                                              acc, t_shift, stream);
+  }
+  SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white};
+  a.rgb = rgb, a.depth = depth, a.acc = acc, a.t_shift = t_shift, a.bg = bg;
+  if (dist) a.inv_range = inv_range, a.dist = dist, a.totals = totals;
+  return seg_composite("nerf_march_seg_composite_fwd_bg", false, dist != nullptr, a, stream);
+}
+
+int nerf_march_seg_composite_bwd_bg(const float* raw, const float* rays, int64_t N, const float* t_table,
+                                    const int32_t* seg_off, const int32_t* out_step, float step_size, int white,
+                                    const float* g_rgb, const float* g_depth, const float* g_acc,
+                                    const float* t_shift, float inv_range, const float* g_dist,
+                                    const double* totals, float* g_raw, const float* bg, hipStream_t stream) {
+  if (!bg) {
+    if (totals)
+      return nerf_march_seg_composite_bwd_dist(raw, rays, N, t_table, seg_off, out_step, step_size, white, g_rgb,
+                                               g_depth, g_acc, t_shift, inv_range, g_dist, totals, g_raw, stream);
+    return nerf_march_seg_composite_bwd_shift(raw, rays, N, t_table, seg_off, out_step, step_size, white, g_rgb,
+                                              g_depth, g_acc, g_raw, t_shift, stream);
+  }
+  SegCompArgs a{raw, rays, N, t_table, seg_off, out_step, step_size, white};
+  a.g_rgb = g_rgb, a.g_depth = g_depth, a.g_acc = g_acc, a.g_raw = g_raw, a.t_shift = t_shift, a.bg = bg;
+  if (totals) a.inv_range = inv_range, a.g_dist = g_dist, a.totals_in = totals;
+  return seg_composite("nerf_march_seg_composite_bwd_bg", true, totals != nullptr, a, stream);
 }
 
 int nerf_march_budget(const int32_t* ray_used, int64_t N, int64_t budget, int32_t* seg_off, int64_t* keep,

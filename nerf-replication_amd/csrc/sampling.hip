@@ -30,9 +30,8 @@ struct RaygenArgs {
   int64_t* pix_out;      // [R] or null
 };
 
-__global__ void raygen_kernel(RaygenArgs a) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.R) return;
+// ray r of either kernel below: its pixel id (given or drawn), pix_out and rays; returns the id
+__device__ __forceinline__ int64_t raygen_ray(const RaygenArgs& a, int64_t r) {
   const int64_t npix = (int64_t)a.H * a.W;
   const int64_t total = npix * a.n_img;
   int64_t id;
@@ -60,11 +59,59 @@ __global__ void raygen_kernel(RaygenArgs a) {
     o[3 + k] = fadd(fadd(fmul(m[4 * k + 0], x), fmul(m[4 * k + 1], y)), fmul(m[4 * k + 2], z));
     o[k] = m[4 * k + 3];
   }
+  return id;
+}
+
+__global__ void raygen_kernel(RaygenArgs a) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.R) return;
+  const int64_t id = raygen_ray(a, r);
   if (a.rgb) {
     const float* src = a.images + id * 3;
     a.rgb[r * 3 + 0] = src[0];
     a.rgb[r * 3 + 1] = src[1];
     a.rgb[r * 3 + 2] = src[2];
+  }
+}
+
+// The same rays from straight-alpha RGBA pixels, composited onto a colour per ray:
+// rgb = C * a + (1 - a) * bg[r], each op rounded on its own (with bg = 1 numpy's white composite of
+// the loader, bit for bit).  bg[r] is given (bg_in) or drawn: words x, y, z of one Philox call on the
+// pixel draw's key and counter with the top bit of the offset's high word set -- offsets are < 2^63, so
+// no pixel draw has that counter.
+struct RaygenRgbaArgs {
+  RaygenArgs g;         // (images unused; rgb [R,3] required)
+  const float* rgba;    // [n_img, H, W, 4]
+  const float* bg_in;   // [R,3] or null (then drawn)
+  float* bg_out;        // [R,3] or null
+};
+
+__global__ void raygen_rgba_kernel(RaygenRgbaArgs a) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.g.R) return;
+  const int64_t id = raygen_ray(a.g, r);
+  float bg[3];
+  if (a.bg_in) {
+    bg[0] = a.bg_in[r * 3 + 0];
+    bg[1] = a.bg_in[r * 3 + 1];
+    bg[2] = a.bg_in[r * 3 + 2];
+  } else {
+    const uint4 c = make_uint4((uint32_t)r, (uint32_t)(r >> 32), (uint32_t)a.g.offset,
+                               (uint32_t)(a.g.offset >> 32) | 0x80000000u);
+    const uint4 q = philox(c, make_uint2((uint32_t)a.g.seed, (uint32_t)(a.g.seed >> 32)));
+    bg[0] = u01(q.x);
+    bg[1] = u01(q.y);
+    bg[2] = u01(q.z);
+  }
+  const float4 px = *(const float4*)(a.rgba + id * 4);  // (a pixel is 16 bytes, the base 16-byte aligned)
+  const float left = fsub(1.f, px.w);
+  a.g.rgb[r * 3 + 0] = fadd(fmul(px.x, px.w), fmul(left, bg[0]));
+  a.g.rgb[r * 3 + 1] = fadd(fmul(px.y, px.w), fmul(left, bg[1]));
+  a.g.rgb[r * 3 + 2] = fadd(fmul(px.z, px.w), fmul(left, bg[2]));
+  if (a.bg_out) {
+    a.bg_out[r * 3 + 0] = bg[0];
+    a.bg_out[r * 3 + 1] = bg[1];
+    a.bg_out[r * 3 + 2] = bg[2];
   }
 }
 
@@ -541,6 +588,20 @@ int nerf_raygen(const float* c2w, int n_img, int H, int W, float focal, const in
   RaygenArgs a{c2w, n_img, H, W, focal, pix, R, seed, offset, images, rays, rgb, pix_out};
   hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, a);
   return check_launch("nerf_raygen");
+}
+
+int nerf_raygen_rgba(const float* c2w, int n_img, int H, int W, float focal, const int64_t* pix, int64_t R,
+                     uint64_t seed, uint64_t offset, const float* images_rgba, const float* bg_in, float* rays,
+                     float* rgb, int64_t* pix_out, float* bg_out, hipStream_t stream) {
+  NERF_REQUIRE(R >= 0 && n_img > 0 && H > 0 && W > 0, "nerf_raygen_rgba: bad sizes");
+  if (R == 0) return 0;
+  NERF_REQUIRE(offset < (1ull << 63), "nerf_raygen_rgba: offset must be < 2^63 (the colour stream owns the top bit)");
+  NERF_REQUIRE(c2w && images_rgba && rays && rgb, "nerf_raygen_rgba: null pointer");
+  NERF_REQUIRE(((uintptr_t)images_rgba & 15) == 0, "nerf_raygen_rgba: images_rgba must be 16-byte aligned");
+  RaygenRgbaArgs a{{c2w, n_img, H, W, focal, pix, R, seed, offset, nullptr, rays, rgb, pix_out}, images_rgba, bg_in,
+                   bg_out};
+  hipLaunchKernelGGL(raygen_rgba_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, a);
+  return check_launch("nerf_raygen_rgba");
 }
 
 int nerf_sample_stratified(const float* rays, int64_t R, int S, const float* t_lin, const float* near,

@@ -86,6 +86,11 @@ SIGNATURES = {
                                                  _p]),
     "nerf_march_seg_composite_bwd_dist": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _f32, _p, _p,
                                                  _p, _p]),
+    "nerf_march_seg_composite_fwd_bg": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _f32, _p, _p, _p,
+                                               _p]),
+    "nerf_march_seg_composite_bwd_bg": (_i32, [_p, _p, _i64, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _f32, _p, _p, _p,
+                                               _p, _p]),
+    "nerf_raygen_rgba": (_i32, [_p, _i32, _i32, _i32, _f32, _p, _i64, _u64, _u64, _p, _p, _p, _p, _p, _p, _p]),
     "nerf_grid_update_points": (_i32, [_i32, _p, _u64, _u64, _u64, _u64, _i64, _i64, _p, _p, _p]),
     "nerf_grid_update_apply": (_i32, [_p, _p, _i64, _i32, _f32, _p, _p]),
     "nerf_grid_update_workspace_bytes": (_i64, [_i32]),

@@ -155,8 +155,14 @@ class kernel_timer:
 # rays
 # --------------------------------------------------------------------------------------
 def raygen(c2w: torch.Tensor, H: int, W: int, focal: float, pix: Optional[torch.Tensor] = None, n_rays: int = 0,
-           seed: int = 0, offset: int = 0, images: Optional[torch.Tensor] = None, want_pix: bool = False):
-    """Pinhole rays for flat pixel ids (img*H*W + j*W + i) -> rays [R,6] (+ rgb [R,3])."""
+           seed: int = 0, offset: int = 0, images: Optional[torch.Tensor] = None, want_pix: bool = False,
+           images_rgba: Optional[torch.Tensor] = None, bg: Optional[torch.Tensor] = None, want_bg: bool = False):
+    """Pinhole rays for flat pixel ids (img*H*W + j*W + i) -> rays [R,6] (+ rgb [R,3]).
+
+    ``images_rgba`` ([n_img,H,W,4] float32, straight alpha) instead of ``images``: the same rays and
+    pixel ids (nerf_raygen_rgba), rgb = C a + (1 - a) bg[r] on a colour per ray -- ``bg`` (float32
+    [R,3]) when given, else drawn from the Philox stream of (seed, offset) -- and a fourth result,
+    the colours (``want_bg``, else None)."""
     c2w = _f32c(c2w.reshape(-1, 4, 4) if c2w.shape[-2:] == (4, 4) else c2w, "c2w")
     if c2w.shape[-2:] != (4, 4):
         raise ValueError("c2w must be [..., 4, 4]")
@@ -167,6 +173,28 @@ def raygen(c2w: torch.Tensor, H: int, W: int, focal: float, pix: Optional[torch.
     rays = torch.empty(R, 6, device=dev, dtype=torch.float32)
     rgb = torch.empty(R, 3, device=dev, dtype=torch.float32) if images is not None else None
     pout = torch.empty(R, device=dev, dtype=torch.int64) if want_pix else None
+    if images_rgba is not None:
+        if images is not None:
+            raise ValueError("raygen: give images or images_rgba, not both")
+        images_rgba = _f32c(images_rgba, "images_rgba")
+        if images_rgba.shape[-1] != 4:
+            raise ValueError(f"images_rgba must be [n_img,H,W,4], got {tuple(images_rgba.shape)}")
+        if bg is not None:
+            bg = _f32c(bg, "bg")
+            if tuple(bg.shape) != (R, 3):
+                raise ValueError(f"bg must be [{R},3] (one colour per ray), got {tuple(bg.shape)}")
+        rgb = torch.empty(R, 3, device=dev, dtype=torch.float32)
+        bout = torch.empty(R, 3, device=dev, dtype=torch.float32) if want_bg else None
+        # bytes per ray: as below with a 16 B pixel, and the colours read (given) or written (want_bg)
+        nbytes = R * (24 + (8 if pix is not None else 0) + (8 if want_pix else 0) + 28
+                      + (12 if bg is not None else 0) + (12 if want_bg else 0))
+        with kernel_timer("raygen_rgba", nbytes, detail=True):
+            check(lib().nerf_raygen_rgba(ptr(c2w), c2w.shape[0], H, W, float(focal), ptr(pix), R, seed, offset,
+                                         ptr(images_rgba), ptr(bg), ptr(rays), ptr(rgb), ptr(pout), ptr(bout),
+                                         stream_of(c2w)), "nerf_raygen_rgba")
+        return rays, rgb, pout, bout
+    if bg is not None or want_bg:
+        raise ValueError("raygen: bg / want_bg need images_rgba")
     if images is not None:
         images = _f32c(images, "images")
     # bytes per ray: pixel id read (given) or written (want_pix), 24 B rays, 12 B rgb gather + 12 B write
@@ -877,6 +905,21 @@ def _shift_arg(t_shift: Optional[torch.Tensor], rays: torch.Tensor) -> Optional[
     return t_shift
 
 
+def _bg_arg(bg: Optional[torch.Tensor], rays: torch.Tensor) -> Optional[torch.Tensor]:
+    """The per-ray background colours of the segment compositor, checked like t_shift: float32 [N,3],
+    contiguous, on the rays' device (TypeError for the dtype, ValueError for the rest), or None."""
+    if bg is None:
+        return None
+    if not torch.is_tensor(bg) or bg.dtype != torch.float32:
+        raise TypeError("bg must be a float32 tensor, got "
+                        f"{bg.dtype if torch.is_tensor(bg) else type(bg).__name__}")
+    if bg.device != rays.device:
+        raise ValueError(f"bg is on {bg.device}, the rays on {rays.device}")
+    if bg.dim() != 2 or tuple(bg.shape) != (rays.shape[0], 3) or not bg.is_contiguous():
+        raise ValueError(f"bg must be contiguous [{rays.shape[0]},3] (one colour per ray), got {tuple(bg.shape)}")
+    return bg
+
+
 def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: torch.Tensor, step_size: float = 0.005,
           t_thresh: float = 1e-4, bbox=SCENE_BBOX, white_bkgd: bool = True, dtype=F32,
           t_table: Optional[torch.Tensor] = None, k_schedule=(12, 24, 48, 96, 192, 384, 768),
@@ -1026,13 +1069,19 @@ class _MarchSegComposite(torch.autograd.Function):
     With ``inv_range`` (a positive float, 1 / (far - near)) the call goes through the ``_dist`` entry
     points instead and returns a fourth map, the distortion of each ray's weights (float32 [N],
     differentiable in raw); rgb, depth and acc keep their bits.  Without it: the three maps and the
-    launches they always had."""
+    launches they always had.
+
+    With ``bg`` (float32 [N,3], a constant: no gradient) the call goes through the ``_bg`` entry
+    points, with or without ``inv_range``: rgb is composited onto bg[r] whatever ``white`` says.
+    Without it: the entry points and launches above."""
 
     @staticmethod
-    def forward(ctx, raw, rays, t_table, seg_off, out_step, step_size, white, t_shift=None, inv_range=None):
+    def forward(ctx, raw, rays, t_table, seg_off, out_step, step_size, white, t_shift=None, inv_range=None,
+                bg=None):
         raw = _f32c(raw.reshape(-1, 4), "raw")
         N, dev = rays.shape[0], rays.device
         t_shift = _shift_arg(t_shift, rays)
+        bg = _bg_arg(bg, rays)
         rgb = torch.empty(N, 3, device=dev, dtype=torch.float32)
         depth = torch.empty(N, device=dev, dtype=torch.float32)
         acc = torch.empty(N, device=dev, dtype=torch.float32)
@@ -1043,6 +1092,18 @@ class _MarchSegComposite(torch.autograd.Function):
         # (what the plain and the dist entry point both begin with)
         head = (ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step), ctx.step_size, ctx.white,
                 ptr(rgb), ptr(depth), ptr(acc), ptr(t_shift))
+        if bg is not None:
+            dist = totals = None
+            if inv_range is not None:
+                dist = torch.empty(N, device=dev, dtype=torch.float32)
+                totals = torch.empty(N, 2, device=dev, dtype=torch.float64)
+            # bytes: as below, and the colour 12 B read per ray
+            with kernel_timer("march_seg_composite_fwd_bg", 20 * M + (60 if dist is None else 80) * N, detail=True):
+                check(lib().nerf_march_seg_composite_fwd_bg(*head, ctx.inv_range or 0.0, ptr(dist), ptr(totals),
+                                                            ptr(bg), stream_of(rays)),
+                      "nerf_march_seg_composite_fwd_bg")
+            ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift, totals, bg)
+            return (rgb, depth, acc) if dist is None else (rgb, depth, acc, dist)
         if inv_range is None:
             # bytes: raw 16 B + step 4 B per point; ray 24 B, offsets 4 B, rgb/depth/acc 20 B per ray
             with kernel_timer("march_seg_composite_fwd", 20 * M + 48 * N, detail=True):
@@ -1062,26 +1123,34 @@ class _MarchSegComposite(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         if all(t is None for t in grads):
-            return (None,) * 9
+            return (None,) * 10
         raw, rays, t_table, seg_off, out_step, t_shift = ctx.saved_tensors[:6]
         N, M = rays.shape[0], raw.shape[0]
         g = [None if t is None else _f32c(t, "cotangent") for t in grads]
         g_raw = torch.empty_like(raw)
         head = (ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step), ctx.step_size, ctx.white,
                 ptr(g[0]), ptr(g[1]), ptr(g[2]))
+        if len(ctx.saved_tensors) == 8:  # (a colour per ray)
+            totals, bg = ctx.saved_tensors[6:]
+            with kernel_timer("march_seg_composite_bwd_bg", 56 * M + (60 if totals is None else 80) * N, detail=True):
+                check(lib().nerf_march_seg_composite_bwd_bg(*head, ptr(t_shift), ctx.inv_range or 0.0,
+                                                            ptr(g[3]) if totals is not None else None, ptr(totals),
+                                                            ptr(g_raw), ptr(bg), stream_of(rays)),
+                      "nerf_march_seg_composite_bwd_bg")
+            return (g_raw,) + (None,) * 9
         if ctx.inv_range is None:
             # bytes: raw 16 B + step 4 B read twice (entry transmittances, then the reverse walk), d_raw 16 B written
             with kernel_timer("march_seg_composite_bwd", 56 * M + 48 * N, detail=True):
                 check(lib().nerf_march_seg_composite_bwd_shift(*head, ptr(g_raw), ptr(t_shift), stream_of(rays)),
                       "nerf_march_seg_composite_bwd")
-            return (g_raw,) + (None,) * 8
+            return (g_raw,) + (None,) * 9
         totals = ctx.saved_tensors[6]
         # bytes: the above, and the cotangent of dist 4 B + the totals 16 B read per ray
         with kernel_timer("march_seg_composite_bwd_dist", 56 * M + 68 * N, detail=True):
             check(lib().nerf_march_seg_composite_bwd_dist(*head, ptr(t_shift), ctx.inv_range, ptr(g[3]),
                                                           ptr(totals), ptr(g_raw), stream_of(rays)),
                   "nerf_march_seg_composite_bwd_dist")
-        return (g_raw,) + (None,) * 8
+        return (g_raw,) + (None,) * 9
 
 
 def march_segments(rays: torch.Tensor, t_table: torch.Tensor, grid_u8: torch.Tensor, macro: Optional[torch.Tensor],
@@ -1127,7 +1196,8 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
                step_size: float = 0.005, t_thresh: float = 1e-4, bbox=SCENE_BBOX, white_bkgd: bool = True, dtype=F32,
                t_table: Optional[torch.Tensor] = None, k_schedule=(12, 24, 48, 96, 192, 384, 768),
                round_bytes: int = 1 << 31, use_macro: bool = True, max_points: Optional[int] = None,
-               t_shift: Optional[torch.Tensor] = None, distortion: bool = False):
+               t_shift: Optional[torch.Tensor] = None, distortion: bool = False,
+               bg: Optional[torch.Tensor] = None):
     """march() whose maps carry an autograd graph back to the packer's parameters: what the
     reference's render_accelerated gives when it is called with autograd on.  Two passes, in the
     spirit of the detached sample_pdf of render().  Pass A is march() itself, without gradient:
@@ -1153,7 +1223,14 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
     ``distortion=True`` adds ``dist_map_f`` (float32 [N], carrying a graph): the distortion of each
     ray's compositing weights on depths normalised by far - near (nerf_march_seg_composite_fwd_dist),
     computed by pass B alone -- under ``max_points`` rows >= rays_kept are 0 with no graph.  The other
-    maps keep their bits."""
+    maps keep their bits.
+
+    ``bg`` (float32 [N,3], contiguous, on the rays' device; a constant of the step) composites pass
+    B's rgb onto a colour per ray instead of the configured background: rgb_map_f[r] = sum w c +
+    (1 - acc[r]) bg[r] (nerf_march_seg_composite_fwd_bg / _bwd_bg).  Pass A never reads it
+    (termination depends on the transmittance alone), so n_queried, depth and acc keep their bits;
+    under ``max_points`` pass B reads bg[:rays_kept] and rows >= rays_kept keep pass A's values."""
+    bg = _bg_arg(bg, rays)
     if distortion and not float(far) > float(near):
         raise ValueError(f"march_grad: distortion needs far > near, got near {near}, far {far}")
     if max_points is not None:
@@ -1185,15 +1262,16 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
     if n_keep < N:  # pass B over the kept rays alone: the first n_keep + 1 offsets are their exclusive prefix sum
         rays_c, vd = rays_c[:n_keep], vd[:n_keep]
         t_shift = None if t_shift is None else t_shift[:n_keep]
+        bg = None if bg is None else bg[:n_keep]
     out_ray, out_step, out_pts = march_segments(rays_c, t_tab, g8, macro, seg_off, M, bbox, t_shift)
     raw = mlp(packer, out_pts, vd, 1, out_ray, dtype)
     if distortion:
         maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd),
-                                        t_shift, 1.0 / (float(far) - float(near)))
+                                        t_shift, 1.0 / (float(far) - float(near)), bg)
         out["dist_map_f"] = maps[3] if n_keep == N else torch.cat([maps[3], maps[3].new_zeros(N - n_keep)], 0)
     else:
         maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd),
-                                        t_shift)
+                                        t_shift, None, bg)
     for k, v in zip(("rgb_map_f", "depth_map_f", "acc_map_f"), maps):
         out[k] = v if n_keep == N else torch.cat([v, out[k][n_keep:]], 0)  # (the dropped rows: pass A's, no graph)
     return out

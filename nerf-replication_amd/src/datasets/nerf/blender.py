@@ -12,6 +12,14 @@ Deliberate difference: the reference draws ``cfg.train.batch_size`` (= 1) rays p
 ``cfg.task_arg.train_rays`` rays (default 4096, BASELINE config 3).  ``batch_rays`` is that count and
 is read at every draw: with ``task_arg.point_budget`` the loss module rewrites it after each training
 step (src/train/trainers/nerf.py), and ``sample_batch(n_rays=)`` serves a caller that has no loader.
+
+``task_arg.train_background: random`` (default ``white``: the above): the TRAIN split keeps the PNGs'
+alpha channel instead -- one copy of its pixels, ``images_rgba`` [N,H,W,4] with straight alpha (1.02 GB
+for 100 lego views against 0.77 GB; ``images``, the white composite, is derived on demand) -- and a train
+batch is composited onto a fresh random colour per ray inside the ray-generation kernel
+(``nerf_raygen_rgba``): ``sample_batch`` returns (rays, rgbs, bg) and the item gains ``bg``.  The colours
+come from the same (seed, draws) as the pixel ids, so they differ per rank and step and add no state.
+Files or arrays without alpha are an error in this mode.  The test split never draws: white, as ever.
 """
 import json
 import os
@@ -32,6 +40,28 @@ def load_png_rgb(path, W=None, H=None):
     if a.shape[-1] == 4:  # RGBA -> RGB on white (blender.py:93-95)
         a = a[..., :3] * a[..., -1:] + (1.0 - a[..., -1:])
     return a[..., :3]
+
+
+def load_png_rgba(path, W=None, H=None):
+    """The PNG as it is stored: [H,W,4] float32 in [0,1], straight alpha.  No alpha channel is an error."""
+    from PIL import Image
+    img = Image.open(path)
+    if W is not None and (img.width, img.height) != (W, H):
+        img = img.resize((W, H), Image.BOX)  # area interpolation (cv2.INTER_AREA)
+    a = np.asarray(img).astype(np.float32) / 255.0
+    if a.ndim != 3 or a.shape[-1] != 4:
+        raise ValueError(f"task_arg.train_background: random needs RGBA images; {path} has no alpha channel")
+    return a
+
+
+def white_composite(rgba):
+    """RGBA -> RGB on white, load_png_rgb's expression (torch or numpy)."""
+    return rgba[..., :3] * rgba[..., -1:] + (1.0 - rgba[..., -1:])
+
+
+def _random_background():
+    from src.models.nerf.renderer.volume_renderer import train_background_setting
+    return train_background_setting(cfg.task_arg) == "random"
 
 
 class Dataset:
@@ -61,20 +91,36 @@ class Dataset:
         cam_x = float(meta["camera_angle_x"])
         self.focal = 0.5 * self.W_orig / np.tan(0.5 * cam_x) * self.input_ratio
         imgs, poses = [], []
+        rgba = self.split == "train" and _random_background()
         for fr in frames:
             p = os.path.join(self.data_root, cfg.scene, fr["file_path"] + ".png")
-            imgs.append(load_png_rgb(p, self.W, self.H))
+            imgs.append((load_png_rgba if rgba else load_png_rgb)(p, self.W, self.H))
             poses.append(np.asarray(fr["transform_matrix"], dtype=np.float32))
-        self.images = torch.from_numpy(np.stack(imgs)).to(self.device)   # [N,H,W,3]
+        if rgba:
+            self.images_rgba = torch.from_numpy(np.stack(imgs)).to(self.device)   # [N,H,W,4]
+        else:
+            self.images = torch.from_numpy(np.stack(imgs)).to(self.device)   # [N,H,W,3]
         self.poses = torch.from_numpy(np.stack(poses)).to(self.device)   # [N,4,4]
         self._setup()
 
     @classmethod
-    def from_arrays(cls, images, poses, focal, split="train"):
-        """A scene given in memory (synthetic benchmarks, tests)."""
+    def from_arrays(cls, images, poses, focal, split="train", alpha=None):
+        """A scene given in memory (synthetic benchmarks, tests).  ``images`` [N,H,W,3], or [N,H,W,4] with
+        straight alpha; ``alpha`` [N,H,W] or [N,H,W,1] gives the channel apart.  With task_arg.train_background:
+        random a train split needs one of the two and keeps the RGBA pixels alone; otherwise the alpha is
+        composited onto white here, as the loader does."""
         self = cls.__new__(cls)
         self.split = split
-        self.images = images
+        if alpha is not None:
+            if images.shape[-1] != 3:
+                raise ValueError(f"from_arrays: alpha goes with [N,H,W,3] images, got {tuple(images.shape)}")
+            images = torch.cat([images, alpha.reshape(*images.shape[:3], 1).to(images)], -1)
+        if split == "train" and _random_background():
+            if images.shape[-1] != 4:
+                raise ValueError("task_arg.train_background: random needs an alpha channel (RGBA images or alpha=)")
+            self.images_rgba = images.contiguous()
+        else:
+            self.images = white_composite(images) if images.shape[-1] == 4 else images
         self.poses = poses
         self.H, self.W = int(images.shape[1]), int(images.shape[2])
         self.focal = float(focal)
@@ -82,17 +128,38 @@ class Dataset:
         self._setup()
         return self
 
+    @property
+    def images(self):
+        """[N,H,W,3]; in random-background mode the white composite of images_rgba, made on demand."""
+        if self._images is None and self.images_rgba is not None:
+            return white_composite(self.images_rgba)
+        return self._images
+
+    @images.setter
+    def images(self, value):
+        self._images = value
+
+    _images = None
+    images_rgba = None  # [N,H,W,4] straight alpha: the train split under task_arg.train_background: random
+
     def _setup(self):
-        self.n_img = int(self.images.shape[0])
+        pixels = self.images_rgba if self.images_rgba is not None else self._images
+        self.n_img = int(pixels.shape[0])
         self.batch_rays = int(cfg.task_arg.get("train_rays", 4096))
         rank = int(os.environ.get("RANK", "0"))
         self.seed = (torch.initial_seed() * 6364136223846793005 + 1442695040888963407 * (rank + 1)) & ((1 << 63) - 1)
         self.draws = 0
 
     def sample_batch(self, n_rays=None):
-        """Uniform random rays over all pixels of all images (blender.py:124-131)."""
+        """Uniform random rays over all pixels of all images (blender.py:124-131) -> (rays, rgbs); with
+        task_arg.train_background: random (rays, rgbs, bg): rgbs composited onto the colours bg [n,3], drawn
+        in the same launch from the same (seed, draws)."""
         n = n_rays or self.batch_rays
         self.draws += 1
+        if self.images_rgba is not None:
+            rays, rgbs, _, bg = ops.raygen(self.poses, self.H, self.W, self.focal, n_rays=n, seed=self.seed,
+                                           offset=self.draws, images_rgba=self.images_rgba, want_bg=True)
+            return rays, rgbs, bg
         rays, rgbs, _ = ops.raygen(self.poses, self.H, self.W, self.focal, n_rays=n, seed=self.seed,
                                    offset=self.draws, images=self.images)
         return rays, rgbs
@@ -104,8 +171,10 @@ class Dataset:
 
     def __getitem__(self, index):
         if self.split == "train":
-            rays, rgbs = self.sample_batch()
+            rays, rgbs, *bg = self.sample_batch()
             ret = {"rays": rays[None], "rgbs": rgbs[None]}
+            if bg:
+                ret["bg"] = bg[0][None]
         else:
             rays, rgbs = self.image_rays(index)
             ret = {"rays": rays[None], "rgbs": rgbs[None], "H": torch.tensor([self.H]),

@@ -37,8 +37,10 @@ def camera_rays(c2w: torch.Tensor, H: int, W: int, focal: float):
     return o, d
 
 
-def shade(o: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
-    """Analytic colour of rays (o, d) [N,3]: nearest hit, Lambert + ambient, white background."""
+def shade(o: torch.Tensor, d: torch.Tensor, with_alpha: bool = False) -> torch.Tensor:
+    """Analytic colour of rays (o, d) [N,3]: nearest hit, Lambert + ambient, white background.
+    ``with_alpha``: [N,4] instead, the same colour and the hit mask as straight alpha (1 on a hit, 0
+    on the background, whose colour stays white)."""
     dn = d / d.norm(dim=-1, keepdim=True)
     N = o.shape[0]
     dev = o.device
@@ -76,7 +78,9 @@ def shade(o: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
     light = light / light.norm()
     lam = AMBIENT + (1.0 - AMBIENT) * (normal * light).sum(-1).clamp_min(0.0)
     rgb = albedo * lam[:, None]
-    return torch.where(torch.isfinite(t_best)[:, None], rgb, torch.ones_like(rgb))
+    hit = torch.isfinite(t_best)[:, None]
+    rgb = torch.where(hit, rgb, torch.ones_like(rgb))
+    return torch.cat([rgb, hit.to(rgb.dtype)], -1) if with_alpha else rgb
 
 
 def view_poses(n: int, seed: int, phi_range=(-60.0, -20.0)) -> torch.Tensor:
@@ -87,15 +91,22 @@ def view_poses(n: int, seed: int, phi_range=(-60.0, -20.0)) -> torch.Tensor:
     return torch.stack([pose_spherical(float(a), float(b), 4.0) for a, b in zip(th, ph)])
 
 
-def make_scene(n_views: int, H: int, W: int, device, seed: int = 0):
-    """-> images [n,H,W,3] fp32, poses [n,4,4] fp32 (device), focal (lego camera angle)."""
+def make_scene(n_views: int, H: int, W: int, device, seed: int = 0, with_alpha: bool = False):
+    """-> images [n,H,W,3] fp32, poses [n,4,4] fp32 (device), focal (lego camera angle).
+    ``with_alpha``: images [n,H,W,4], straight alpha (make_scene_rgba)."""
     poses = view_poses(n_views, seed).to(device)
     focal = focal_for(W)
     imgs = []
     for k in range(n_views):
         o, d = camera_rays(poses[k], H, W, focal)
-        imgs.append(shade(o, d).reshape(H, W, 3))
+        imgs.append(shade(o, d, with_alpha).reshape(H, W, 4 if with_alpha else 3))
     return torch.stack(imgs), poses, focal
+
+
+def make_scene_rgba(n_views: int, H: int, W: int, device, seed: int = 0):
+    """make_scene with the alpha channel kept: images [n,H,W,4], alpha 1 on a hit and 0 elsewhere.
+    Its white composite rgb * a + (1 - a) is make_scene's images bit for bit."""
+    return make_scene(n_views, H, W, device, seed, with_alpha=True)
 
 
 def psnr(pred: torch.Tensor, gt: torch.Tensor) -> float:

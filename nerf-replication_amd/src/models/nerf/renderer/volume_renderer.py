@@ -61,6 +61,20 @@ def distortion_loss_setting(task_arg) -> float:
     return float(v)
 
 
+TRAIN_BACKGROUNDS = ("white", "random")
+
+
+def train_background_setting(task_arg) -> str:
+    """task_arg.train_background ("white" | "random", default "white"): what the training march and its ground
+    truth are composited onto -- the configured background, or a fresh random colour per ray and step."""
+    v = task_arg.get("train_background", "white")
+    if v is None:
+        return "white"
+    if not isinstance(v, str) or v not in TRAIN_BACKGROUNDS:
+        raise ValueError(f"task_arg.train_background must be one of {TRAIN_BACKGROUNDS}, got {v!r}")
+    return v
+
+
 class Renderer:
     def __init__(self, net):
         self.net = net
@@ -226,7 +240,7 @@ class Renderer:
         idx, _ = ops.grid_index(points, None, int(self.grid_resolution[0]), self._bbox_tuple())
         return idx
 
-    def _render_accelerated_grad(self, rays_flat, near, far):
+    def _render_accelerated_grad(self, rays_flat, near, far, bg=None):
         """render_accelerated under autograd (ops.march_grad): the maps carry a graph back to the fine
         net, as the reference's plain-torch march does.  Rays in chunks of task_arg.chunk_size,
         concatenated, as render() does; no device-wide synchronisation (render_time is host time).
@@ -239,8 +253,18 @@ class Renderer:
         Only this path jitters: the no-grad march of render_accelerated never does.
         With task_arg.distortion_loss_weight > 0 the result also has dist_map_f (the distortion of each
         ray's weights, with a graph), concatenated over the chunks like the other maps; the no-grad
-        march never computes it."""
+        march never computes it.
+        With task_arg.train_background: random the batch's colours ``bg`` [N,3] go to the segment compositor
+        (ops.march_grad(bg=)): bg[i:i + chunk] per chunk, the whole tensor under a point budget, so a chunked
+        step equals the unchunked one.  With the key at white ``bg`` is not looked at."""
         ta = cfg.task_arg
+        if train_background_setting(ta) != "random":
+            bg = None
+        elif bg is None:
+            raise ValueError("task_arg.train_background: random needs the batch's colours (batch['bg'], which the "
+                             "train dataset adds under this key)")
+        else:
+            bg = bg.reshape(-1, 3)
         distortion = distortion_loss_setting(ta) > 0.0
         start = time.time()
         chunk = self._chunk(True)
@@ -256,7 +280,7 @@ class Renderer:
                                  step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
                                  bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
                                  k_schedule=sched, max_points=int(self.max_points), t_shift=t_shift,
-                                 distortion=distortion)
+                                 distortion=distortion, bg=bg)
             keys = ("rgb_map_f", "depth_map_f", "acc_map_f", "n_queried", "n_evaluated", "rounds", "rays_kept",
                     "n_points") + (("dist_map_f",) if distortion else ())
             ret = {k: out[k] for k in keys}
@@ -273,7 +297,7 @@ class Renderer:
                                  step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
                                  bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
                                  k_schedule=sched, t_shift=None if t_shift is None else t_shift[i:i + chunk],
-                                 distortion=distortion)
+                                 distortion=distortion, bg=None if bg is None else bg[i:i + chunk])
             for k, v in maps.items():
                 v.append(out[k])
             for k in counts:
@@ -298,7 +322,7 @@ class Renderer:
         near = float(batch["near"].reshape(-1)[0]) if torch.is_tensor(batch["near"]) else float(batch["near"])
         far = float(batch["far"].reshape(-1)[0]) if torch.is_tensor(batch["far"]) else float(batch["far"])
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.net.model_fine.parameters()):
-            return self._render_accelerated_grad(rays_flat, near, far)
+            return self._render_accelerated_grad(rays_flat, near, far, batch.get("bg"))
         starter = torch.cuda.Event(enable_timing=True)
         ender = torch.cuda.Event(enable_timing=True)
         starter.record()

@@ -44,6 +44,15 @@ distortion of each ray's compositing weights to the training loss: loss = MSE + 
 the mean over the rays the MSE runs over (the first ``rays_kept`` under a point budget), stats gain
 ``loss_dist`` (the unweighted mean).  Per rank, like the MSE: no collective.  Exactly 0 computes nothing:
 every launch, output and stats key is what it was.  Validation never computes it.
+
+``task_arg.train_background: random`` (default ``white``; only with ``train_renderer: accelerated``, either
+``train_grid``, with or without a point budget, jitter or the distortion term) trains on a fresh random
+background colour per ray and step: the train dataset keeps the alpha channel and its batch carries ``bg``
+[N,3] and ``rgbs`` already composited onto it (nerf_raygen_rgba); the training march composites its
+prediction onto the same colours (Renderer._render_accelerated_grad -> ops.march_grad(bg=)), so density where
+the image is transparent costs loss whatever its colour.  The loss itself is unchanged (``gt`` arrives
+blended).  A batch without ``bg`` is an error.  Validation, evaluation and every other no-grad march keep the
+configured background.  With ``white`` every launch, output and stats key is what it was.
 """
 import os
 
@@ -55,7 +64,8 @@ from nerf_amd import ops
 from src.config import cfg
 from src.models.nerf.renderer.online_grid import OnlineGrid, grid_update_settings
 from src.models.nerf.renderer.ray_budget import RayBudget
-from src.models.nerf.renderer.volume_renderer import Renderer, distortion_loss_setting, march_jitter_setting
+from src.models.nerf.renderer.volume_renderer import (Renderer, distortion_loss_setting, march_jitter_setting,
+                                                        train_background_setting)
 
 TRAIN_RENDERERS = ("hierarchical", "accelerated")
 TRAIN_GRIDS = ("file", "online")
@@ -91,6 +101,10 @@ class NetworkWrapper(nn.Module):
         if self.distortion_weight > 0.0 and self.train_renderer != "accelerated":
             raise ValueError("task_arg.distortion_loss_weight > 0 regularises the weights of train_renderer: "
                              f"accelerated; with train_renderer: {self.train_renderer} there is no such term")
+        self.train_background = train_background_setting(cfg.task_arg)
+        if self.train_background == "random" and self.train_renderer != "accelerated":
+            raise ValueError("task_arg.train_background: random composites train_renderer: accelerated onto a colour "
+                             f"per ray; with train_renderer: {self.train_renderer} the background is white_bkgd's")
         self.ray_budget = RayBudget.from_config(cfg.task_arg)  # (None: point_budget.target 0, the fixed train_rays)
         if self.ray_budget is not None:
             self.renderer.max_points = self.ray_budget.max_points
@@ -181,6 +195,9 @@ class NetworkWrapper(nn.Module):
     def forward(self, batch):
         gt = batch["rgbs"].reshape(-1, 3) if batch["rgbs"].dim() == 3 else batch["rgbs"]
         budgeted = self.ray_budget is not None and torch.is_grad_enabled()
+        if self.train_background == "random" and torch.is_grad_enabled() and batch.get("bg") is None:
+            raise ValueError("task_arg.train_background: random needs batch['bg'] (the colours the ground truth was "
+                             "composited onto); the train dataset adds it under this key")
         if self.online_grid is not None:
             grid = self._live_grid(batch["rays"].device)
             fine = self.net.model_fine

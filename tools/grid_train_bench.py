@@ -4,6 +4,7 @@ from-scratch run through the march converges against the hierarchical one.
     python tools/grid_train_bench.py [--tiers fp32,bf16x3f] [--out profiles/r8/online_grid.json]
     python tools/grid_train_bench.py --jitter [--out profiles/r10/march_jitter.json]
     python tools/grid_train_bench.py --distortion 0.001,0.01 [--out profiles/r11/distortion.json]
+    python tools/grid_train_bench.py --background random [--out profiles/r13/random_background.json]
 
 One process, HIP events on the compute stream, medians.
 
@@ -23,6 +24,9 @@ convergence the procedural scene (src/datasets/nerf/synthetic.py), seed-0 init, 
             (same scene, seed, ray stream, steps and tiers), merged into --out under "convergence".
 --distortion W[,W...]  the convergence part alone, online-accelerated with task_arg.distortion_loss_weight 0 and
             each W (same scene, seed, ray stream, steps and tiers), merged into --out under "convergence".
+--background random  the convergence part alone, online-accelerated with task_arg.train_background white and
+            random (the same scene with its alpha channel, seed, ray stream, steps and tiers; the held-out
+            views stay composited on white), merged into --out under "convergence".
 """
 import argparse
 import json
@@ -67,22 +71,25 @@ def main():
                     help="convergence only: online-accelerated with train_march_jitter off and on")
     ap.add_argument("--distortion", default=None, metavar="W[,W...]",
                     help="convergence only: online-accelerated with distortion_loss_weight 0 and each W")
+    ap.add_argument("--background", default=None, choices=("random",),
+                    help="convergence only: online-accelerated with train_background white and random")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dist_weights = [float(w) for w in a.distortion.split(",")] if a.distortion else []
-    if a.jitter and dist_weights:
-        ap.error("--jitter and --distortion are separate runs")
+    if a.jitter + bool(dist_weights) + bool(a.background) > 1:
+        ap.error("--jitter, --distortion and --background are separate runs")
     if any(not w > 0 for w in dist_weights):
         ap.error("--distortion takes positive weights (the run with the weight 0 is always made)")
-    conv_only = a.jitter or bool(dist_weights)
+    conv_only = a.jitter or bool(dist_weights) or bool(a.background)
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", *(("r10", "march_jitter.json") if a.jitter else
                                                  ("r11", "distortion.json") if dist_weights else
+                                                 ("r13", "random_background.json") if a.background else
                                                  ("r8", "online_grid.json")))
     from nerf_amd import ops
     from src.config import cfg
     from src.datasets.nerf.blender import Dataset
-    from src.datasets.nerf.synthetic import camera_rays, make_scene, psnr, shade, view_poses
+    from src.datasets.nerf.synthetic import camera_rays, make_scene, make_scene_rgba, psnr, shade, view_poses
     from src.models import make_network
     from src.models.nerf.network import Network
     from src.models.nerf.renderer.online_grid import DEFAULTS, OnlineGrid
@@ -184,7 +191,8 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- convergence from scratch --------------------------------------------------------------------
-    imgs, poses, focal = make_scene(100, 100, 100, dev, seed=0)
+    # (with --background the views keep their alpha; composited on white they are make_scene's bit for bit)
+    imgs, poses, focal = (make_scene_rgba if a.background else make_scene)(100, 100, 100, dev, seed=0)
     ev_poses = view_poses(4, seed=1).to(dev)
     held = []
     for k in range(ev_poses.shape[0]):
@@ -198,8 +206,11 @@ def main():
                                                                                       "hierarchical")
         if dist_weights:
             modes = ("online_accelerated",) + tuple(f"online_accelerated_distortion_{w:g}" for w in dist_weights)
+        if a.background:
+            modes = ("online_accelerated", "online_accelerated_background_random")
         for mode in modes:
             ta.mlp_dtype = dtype
+            ta.train_background = "random" if mode.endswith("_background_random") else "white"
             ta.perturb = 1
             ta.train_march_jitter = mode == "online_accelerated_jitter"
             ta.distortion_loss_weight = float(mode.rsplit("_", 1)[1]) if "_distortion_" in mode else 0.0
@@ -228,8 +239,11 @@ def main():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(min(a.every, a.steps - s0)):
-                    r, c = ds.sample_batch()
-                    out, _, _ = trainer.train_step({"rays": r[None], "rgbs": c[None], "near": near, "far": far}, opt)
+                    r, c, *bg = ds.sample_batch()
+                    b = {"rays": r[None], "rgbs": c[None], "near": near, "far": far}
+                    if bg:
+                        b["bg"] = bg[0][None]
+                    out, _, _ = trainer.train_step(b, opt)
                 torch.cuda.synchronize()
                 train_s += time.perf_counter() - t0
                 if "n_queried" in out:
@@ -247,6 +261,7 @@ def main():
     reset_modes()
     ta.train_march_jitter = False
     ta.distortion_loss_weight = 0.0
+    ta.train_background = "white"
 
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     if conv_only:  # the file also holds the cost measurements of other tools: only this part is replaced
