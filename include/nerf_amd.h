@@ -399,6 +399,40 @@ int64_t nerf_grid_update_workspace_bytes(int res);
 int nerf_grid_update_threshold(const float* density, int res, float threshold, void* workspace, uint8_t* grid,
                                void* stats, hipStream_t stream);
 
+/* ---- mesh export: the level set of a density lattice as an indexed triangle mesh ---------------------
+ * Stands in for extract_mesh (src/utils/mesh_utils.py:8-46; its skimage / trimesh calls no longer
+ * exist).  Marching tetrahedra on the Kuhn split: every lattice cube is cut into the six tetrahedra
+ * p, p + e_a, p + e_a + e_b, p + (1,1,1), one per permutation (a, b, c) of the axes -- translation
+ * invariant, no ambiguous case.  (Added within ABI 4.)
+ *
+ * Lattice: nx x ny x nz points, every axis >= 2, nx*ny*nz < 2^31 (-22 otherwise); point (ix,iy,iz) has
+ * index (ix*ny + iy)*nz + iz and coordinate fadd(mn[a], fmul((float)i, h[a])) on axis a, h[a] =
+ * fdiv(fsub(mx[a], mn[a]), (float)(n[a] - 1)), each op rounded on its own: both bbox faces are sampled.
+ * bbox_host is six host floats (min xyz, max xyz).  A point is inside when field >= level; the field
+ * must be finite (the caller checks).
+ *
+ * Point p owns the edges p -> p + d, d = (1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1)
+ * (types 0..6) that stay in the lattice.  An owned edge whose ends differ in "inside" carries one
+ * vertex, t = fdiv(fsub(level, f0), fsub(f1, f0)) from the owner end, v[a] = fadd(x0[a], fmul(t,
+ * fsub(x1[a], x0[a]))).  Vertex id = vert_off[p] + popcount(edge_mask[p] & ((1 << type) - 1)): lattice
+ * order, then edge type -- welded without a hash, a sort or an atomic; verts is a pure function of the
+ * field.  Faces: per tetrahedron one triangle (1 or 3 vertices inside) or two (2 inside), wound so that
+ * the right-hand normal points from inside to outside; per cube in permutation order.
+ *
+ * nerf_mesh_lattice: pts [(x1-x0)*ny*nz, 3] of the x-planes [x0, x1) (the field slab by slab).
+ * nerf_mesh_classify: edge_mask [P] (bit t: the edge of type t crosses), vert_count [P] = its
+ *   popcount, tri_count [(nx-1)(ny-1)(nz-1)] per cube ((ix*(ny-1) + iy)*(nz-1) + iz).
+ * nerf_mesh_emit: vert_off [P] / tri_off [cubes] are the caller's exclusive prefix sums of the counts,
+ *   n_verts / n_faces their totals (n_verts < 2^31: ids are int32; nothing is written past either);
+ *   writes verts [n_verts,3] and faces [n_faces,3].  No allocation, no host synchronisation, no
+ *   atomics: the same bytes on every run. */
+int nerf_mesh_lattice(const float* bbox_host, int nx, int ny, int nz, int x0, int x1, float* pts, hipStream_t stream);
+int nerf_mesh_classify(const float* field, int nx, int ny, int nz, float level, uint8_t* edge_mask,
+                       int32_t* vert_count, int32_t* tri_count, hipStream_t stream);
+int nerf_mesh_emit(const float* field, const float* bbox_host, int nx, int ny, int nz, float level,
+                   const uint8_t* edge_mask, const int64_t* vert_off, const int64_t* tri_off, int64_t n_verts,
+                   int64_t n_faces, float* verts, int32_t* faces, hipStream_t stream);
+
 /* ---- (a10) clip_grad_value_ + Adam (src/train/trainers/trainer.py:61-62, optimizer.py:8-28) ---- */
 int nerf_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
                    double beta2, double eps, int64_t step, double clip_value, hipStream_t stream);

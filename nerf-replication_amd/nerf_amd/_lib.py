@@ -95,6 +95,9 @@ SIGNATURES = {
     "nerf_grid_update_apply": (_i32, [_p, _p, _i64, _i32, _f32, _p, _p]),
     "nerf_grid_update_workspace_bytes": (_i64, [_i32]),
     "nerf_grid_update_threshold": (_i32, [_p, _i32, _f32, _p, _p, _p, _p]),
+    "nerf_mesh_lattice": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    "nerf_mesh_classify": (_i32, [_p, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
+    "nerf_mesh_emit": (_i32, [_p, _p, _i32, _i32, _i32, _f32, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     "nerf_metrics_workspace_bytes": (_i64, [_i32, _i32]),
     "nerf_image_metrics": (_i32, [_p, _p, _i32, _i32, _p, _p, _p]),
     "nerf_adam_step": (_i32, [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _p]),

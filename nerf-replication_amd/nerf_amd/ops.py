@@ -13,6 +13,7 @@ Reference interfaces mirrored (echo636/nerf-replication):
   march_budget         (no counterpart) the segment layout of march_grad(max_points=) under a point cap
   bake                 occupancy_grid.py:15-80
   adam_step            src/train/trainers/trainer.py:61-62
+  mesh_extract         src/utils/mesh_utils.py:8-46 (the surface extraction; mesh_field is its density loop)
 """
 from __future__ import annotations
 
@@ -1275,6 +1276,116 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
     for k, v in zip(("rgb_map_f", "depth_map_f", "acc_map_f"), maps):
         out[k] = v if n_keep == N else torch.cat([v, out[k][n_keep:]], 0)  # (the dropped rows: pass A's, no graph)
     return out
+
+
+# --------------------------------------------------------------------------------------
+# mesh export (csrc/mesh.hip: marching tetrahedra on the Kuhn split of a density lattice)
+# --------------------------------------------------------------------------------------
+MESH_MLP_POINTS = 2097152  # the points of a full 128^3 grid update: the default bound of one mesh_field MLP launch
+
+
+def _mesh_shape(shape):
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 3 or min(shape) < 2:
+        raise ValueError(f"mesh lattice needs three axes of at least 2 points, got {shape}")
+    if shape[0] * shape[1] * shape[2] > 2 ** 31 - 1:
+        raise ValueError(f"mesh lattice {shape} has more than 2^31 - 1 points")
+    return shape
+
+
+def mesh_lattice(shape, bbox=SCENE_BBOX, x0: int = 0, x1: Optional[int] = None, device=None) -> torch.Tensor:
+    """The lattice points of the x-planes [x0, x1) -> fp32 [(x1-x0)*ny*nz, 3], z fastest: coordinate i of
+    axis a is mn[a] + float(i) * ((mx[a] - mn[a]) / float(n[a] - 1)), each op rounded on its own, so both
+    bbox faces are sampled (nerf_mesh_lattice)."""
+    nx, ny, nz = _mesh_shape(shape)
+    x1 = nx if x1 is None else int(x1)
+    x0 = int(x0)
+    if not 0 <= x0 <= x1 <= nx:
+        raise ValueError(f"mesh_lattice: x-planes [{x0}, {x1}) outside [0, {nx})")
+    device = torch.device(device if device is not None else "cuda")
+    if device.type != "cuda":
+        raise RuntimeError("nerf_amd kernels run on the GPU only (got a CPU device); there is no CPU fallback")
+    pts = torch.empty((x1 - x0) * ny * nz, 3, dtype=torch.float32, device=device)
+    check(lib().nerf_mesh_lattice(_bbox_arr(bbox), nx, ny, nz, x0, x1, ptr(pts), stream_of(pts)), "nerf_mesh_lattice")
+    return pts
+
+
+def mesh_field(packer: PackedMLP, shape, bbox=SCENE_BBOX, dtype=F32, slab_planes: Optional[int] = None) -> torch.Tensor:
+    """sigma = relu(raw[:, 3]) of the density-only MLP on the whole lattice -> fp32 [nx,ny,nz], evaluated in
+    slabs of ``slab_planes`` x-planes (default: as many as keep one MLP launch at or below MESH_MLP_POINTS)."""
+    nx, ny, nz = _mesh_shape(shape)
+    if slab_planes is None:
+        slab_planes = max(1, MESH_MLP_POINTS // (ny * nz))
+    slab_planes = int(slab_planes)
+    if slab_planes < 1:
+        raise ValueError(f"mesh_field: slab_planes must be >= 1, got {slab_planes}")
+    device = packer.params[0].device
+    sigma = torch.empty(nx, ny, nz, dtype=torch.float32, device=device)
+    with torch.no_grad():
+        for x0 in range(0, nx, slab_planes):
+            x1 = min(nx, x0 + slab_planes)
+            raw = mlp(packer, mesh_lattice((nx, ny, nz), bbox, x0, x1, device), None, 1, None, dtype, density_only=True)
+            sigma[x0:x1] = torch.relu(raw[:, 3]).reshape(x1 - x0, ny, nz)
+    return sigma
+
+
+def _mesh_check(field: torch.Tensor, level: float):
+    if not field.is_cuda:
+        raise RuntimeError("nerf_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if field.dtype != torch.float32 or field.dim() != 3:
+        raise TypeError(f"mesh_extract: field must be a float32 [nx,ny,nz] tensor, got {field.dtype} {tuple(field.shape)}")
+    import math
+    if not math.isfinite(float(level)):
+        raise ValueError(f"mesh_extract: level must be a finite number, got {level}")
+    return _mesh_shape(field.shape)
+
+
+def mesh_classify(field: torch.Tensor, level: float):
+    """-> edge_mask uint8 [P], vert_count int32 [P], tri_count int32 [cubes] (nerf_mesh_classify)."""
+    nx, ny, nz = _mesh_check(field, level)
+    dev = field.device
+    mask = torch.empty(nx * ny * nz, dtype=torch.uint8, device=dev)
+    vcount = torch.empty(nx * ny * nz, dtype=torch.int32, device=dev)
+    tcount = torch.empty((nx - 1) * (ny - 1) * (nz - 1), dtype=torch.int32, device=dev)
+    check(lib().nerf_mesh_classify(ptr(field), nx, ny, nz, float(level), ptr(mask), ptr(vcount), ptr(tcount),
+                                   stream_of(field)), "nerf_mesh_classify")
+    return mask, vcount, tcount
+
+
+def mesh_scan(vcount: torch.Tensor, tcount: torch.Tensor):
+    """The exclusive prefix sums of the two counts (int64) and their totals as a device [2] tensor."""
+    vinc = torch.cumsum(vcount, 0, dtype=torch.int64)
+    tinc = torch.cumsum(tcount, 0, dtype=torch.int64)
+    totals = torch.stack([vinc[-1], tinc[-1]])
+    return vinc.sub_(vcount), tinc.sub_(tcount), totals
+
+
+def mesh_emit(field: torch.Tensor, level: float, bbox, mask, voff, toff, V: int, F: int):
+    """-> verts fp32 [V,3], faces int32 [F,3] (nerf_mesh_emit)."""
+    nx, ny, nz = _mesh_check(field, level)
+    verts = torch.empty(V, 3, dtype=torch.float32, device=field.device)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=field.device)
+    check(lib().nerf_mesh_emit(ptr(field), _bbox_arr(bbox), nx, ny, nz, float(level), ptr(mask), ptr(voff), ptr(toff),
+                               V, F, ptr(verts), ptr(faces), stream_of(field)), "nerf_mesh_emit")
+    return verts, faces
+
+
+def mesh_extract(field: torch.Tensor, level: float, bbox=SCENE_BBOX):
+    """The level set {field == level} of a fp32 [nx,ny,nz] device lattice over ``bbox`` as an indexed, welded
+    triangle mesh -> (verts fp32 [V,3], faces int32 [F,3]) on the device; normals point from field >= level to
+    field < level.  Marching tetrahedra on the Kuhn split (DESIGN.md 4 "Mesh export"): closed wherever the
+    surface stays off the lattice boundary, the same bytes on every run.  One host read (V, F and the
+    finiteness of the field together); a non-finite field raises."""
+    _mesh_check(field, level)
+    field = field.contiguous()
+    mask, vcount, tcount = mesh_classify(field, level)
+    voff, toff, totals = mesh_scan(vcount, tcount)
+    V, F, finite = torch.cat([totals, torch.isfinite(field).all().to(torch.int64).reshape(1)]).tolist()
+    if not finite:
+        raise ValueError("mesh_extract: the field holds a NaN or an infinity")
+    if V >= 2 ** 31:
+        raise ValueError(f"mesh_extract: {V} vertices do not fit int32 ids; lower the resolution")
+    return mesh_emit(field, level, bbox, mask, voff, toff, V, F)
 
 
 # --------------------------------------------------------------------------------------

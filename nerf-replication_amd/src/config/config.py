@@ -115,6 +115,7 @@ def default_cfg() -> CfgNode:
                   "scheduler": {"type": "exponential", "gamma": 0.1, "decay_epochs": 500}},
         "test": {"batch_size": 1, "epoch": -1},
         "eval": {"whole_img": True},
+        "level": 32.0, "resolution": 256,  # extract_mesh (config.py:10-12)
     })
 
 
