@@ -890,35 +890,29 @@ def march_jitter(n: int, step_size: float, seed: int, offset: int, device) -> to
     return out
 
 
-def _shift_arg(t_shift: Optional[torch.Tensor], rays: torch.Tensor) -> Optional[torch.Tensor]:
-    """A per-ray shift as the kernels read it: fp32, contiguous, [N], on the rays' device (no
-    conversion: both passes of a differentiable march must read the very same values)."""
-    if t_shift is None:
+def _per_ray_arg(t: Optional[torch.Tensor], rays: torch.Tensor, name: str, tail: tuple, noun: str):
+    """A per-ray argument as the kernels read it: float32, contiguous, [N, *tail], on the rays' device, or None
+    (TypeError for the dtype, ValueError for the rest).  No conversion: both passes of a differentiable march
+    must read the very same values.  ``noun``: what a ray has one of, for the message."""
+    if t is None:
         return None
-    if not torch.is_tensor(t_shift) or t_shift.dtype != torch.float32:
-        raise TypeError("t_shift must be a float32 tensor, got "
-                        f"{t_shift.dtype if torch.is_tensor(t_shift) else type(t_shift).__name__}")
-    if t_shift.device != rays.device:
-        raise ValueError(f"t_shift is on {t_shift.device}, the rays on {rays.device}")
-    if t_shift.dim() != 1 or t_shift.shape[0] != rays.shape[0] or not t_shift.is_contiguous():
-        raise ValueError(f"t_shift must be contiguous [{rays.shape[0]}] (one shift per ray), "
-                         f"got {tuple(t_shift.shape)}")
-    return t_shift
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise TypeError(f"{name} must be a float32 tensor, got "
+                        f"{t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    if t.device != rays.device:
+        raise ValueError(f"{name} is on {t.device}, the rays on {rays.device}")
+    shape = (rays.shape[0],) + tail
+    if tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous [{','.join(map(str, shape))}] (one {noun} per ray), "
+                         f"got {tuple(t.shape)}")
+    return t
 
 
-def _bg_arg(bg: Optional[torch.Tensor], rays: torch.Tensor) -> Optional[torch.Tensor]:
-    """The per-ray background colours of the segment compositor, checked like t_shift: float32 [N,3],
-    contiguous, on the rays' device (TypeError for the dtype, ValueError for the rest), or None."""
-    if bg is None:
-        return None
-    if not torch.is_tensor(bg) or bg.dtype != torch.float32:
-        raise TypeError("bg must be a float32 tensor, got "
-                        f"{bg.dtype if torch.is_tensor(bg) else type(bg).__name__}")
-    if bg.device != rays.device:
-        raise ValueError(f"bg is on {bg.device}, the rays on {rays.device}")
-    if bg.dim() != 2 or tuple(bg.shape) != (rays.shape[0], 3) or not bg.is_contiguous():
-        raise ValueError(f"bg must be contiguous [{rays.shape[0]},3] (one colour per ray), got {tuple(bg.shape)}")
-    return bg
+# the march's options, by name: the ones march() and march_grad() share and hand to _march() as they got them,
+# and the ones of the no-grad rounds that march() alone exposes (march_grad leaves them at _march()'s defaults)
+_WALK_OPTIONS = ("step_size", "t_thresh", "bbox", "white_bkgd", "dtype", "t_table", "k_schedule", "round_bytes",
+                 "use_macro", "t_shift")
+_ROUND_OPTIONS = ("k_low", "t_split", "sync_every", "one_pass", "k_low_grow", "return_used")
 
 
 def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: torch.Tensor, step_size: float = 0.005,
@@ -957,10 +951,8 @@ def march(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, grid: 
     rounds (ray_used.sum() == n_queried); the other outputs are the same bit for bit.  ``t_shift``
     (float32 [N], ops.march_jitter) moves ray r's steps to t_table + t_shift[r] (one rounded fp32
     add per step, the skip still exact); None is the table as it is, with the same launches."""
-    return _march(packer, rays, near, far, grid, step_size=step_size, t_thresh=t_thresh, bbox=bbox,
-                  white_bkgd=white_bkgd, dtype=dtype, t_table=t_table, k_schedule=k_schedule, round_bytes=round_bytes,
-                  k_low=k_low, t_split=t_split, sync_every=sync_every, use_macro=use_macro, one_pass=one_pass,
-                  k_low_grow=k_low_grow, return_used=return_used, t_shift=t_shift)[0]
+    given = locals()
+    return _march(packer, rays, near, far, grid, **{k: given[k] for k in _WALK_OPTIONS + _ROUND_OPTIONS})[0]
 
 
 def _march(packer, rays, near, far, grid, *, step_size, t_thresh, bbox, white_bkgd, dtype, t_table, k_schedule,
@@ -974,7 +966,7 @@ def _march(packer, rays, near, far, grid, *, step_size, t_thresh, bbox, white_bk
     numbers: no further synchronisation): the result gains seg_off (int32 [N+1]), rays_kept, n_points."""
     rays = _f32c(rays.reshape(-1, 6), "rays")
     dev, N = rays.device, rays.shape[0]
-    t_shift = _shift_arg(t_shift, rays)
+    t_shift = _per_ray_arg(t_shift, rays, "t_shift", (), "shift")
     L = lib()
     s = stream_of(rays)
     if N == 0:
@@ -1063,6 +1055,19 @@ def _march(packer, rays, near, far, grid, *, step_size, t_thresh, bbox, white_bk
     return out, (rays, t_table, n_steps, g, res, macro, vd)
 
 
+# The segment compositor's variants, by (a colour per ray, a distortion term): the C entry points of the forward
+# and the backward, the suffix of their kernel_timer names and check() labels, and the bytes moved per ray.
+# Plain: ray 24 B, offsets 4 B, rgb/depth/acc 20 B (or their cotangents); dist adds the map (or its cotangent)
+# 4 B and the fp64 totals 16 B; bg adds the colour 12 B.  Per point, whatever the variant: raw 16 B + step 4 B in
+# the forward; both read twice (entry transmittances, then the reverse walk) and d_raw 16 B written in the backward
+_SEG_COMPOSITE = {
+    (False, False): ("nerf_march_seg_composite_fwd_shift", "nerf_march_seg_composite_bwd_shift", "", 48),
+    (False, True): ("nerf_march_seg_composite_fwd_dist", "nerf_march_seg_composite_bwd_dist", "_dist", 68),
+    (True, False): ("nerf_march_seg_composite_fwd_bg", "nerf_march_seg_composite_bwd_bg", "_bg", 60),
+    (True, True): ("nerf_march_seg_composite_fwd_bg", "nerf_march_seg_composite_bwd_bg", "_bg", 80),
+}
+
+
 class _MarchSegComposite(torch.autograd.Function):
     """Compositing of per-ray segments of marched points (nerf_march_seg_composite_fwd / _bwd):
     differentiable in raw, every point of a segment used (the march decided which, without grad).
@@ -1074,83 +1079,61 @@ class _MarchSegComposite(torch.autograd.Function):
 
     With ``bg`` (float32 [N,3], a constant: no gradient) the call goes through the ``_bg`` entry
     points, with or without ``inv_range``: rgb is composited onto bg[r] whatever ``white`` says.
-    Without it: the entry points and launches above."""
+    Without it: the entry points and launches above.
+
+    Which of the four variants a call is (``ctx.variant``: a colour per ray, a distortion term) is fixed in the
+    forward; _SEG_COMPOSITE has what differs between them but the arguments."""
 
     @staticmethod
     def forward(ctx, raw, rays, t_table, seg_off, out_step, step_size, white, t_shift=None, inv_range=None,
                 bg=None):
         raw = _f32c(raw.reshape(-1, 4), "raw")
-        N, dev = rays.shape[0], rays.device
-        t_shift = _shift_arg(t_shift, rays)
-        bg = _bg_arg(bg, rays)
-        rgb = torch.empty(N, 3, device=dev, dtype=torch.float32)
-        depth = torch.empty(N, device=dev, dtype=torch.float32)
-        acc = torch.empty(N, device=dev, dtype=torch.float32)
-        M = raw.shape[0]
+        N, M, dev = rays.shape[0], raw.shape[0], rays.device
+        t_shift = _per_ray_arg(t_shift, rays, "t_shift", (), "shift")
+        bg = _per_ray_arg(bg, rays, "bg", (3,), "colour")
         ctx.set_materialize_grads(False)
         ctx.step_size, ctx.white = float(step_size), int(bool(white))
         ctx.inv_range = None if inv_range is None else float(inv_range)
-        # (what the plain and the dist entry point both begin with)
-        head = (ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step), ctx.step_size, ctx.white,
+        ctx.variant = (bg is not None, inv_range is not None)
+        fwd, _, label, ray_bytes = _SEG_COMPOSITE[ctx.variant]
+        rgb = torch.empty(N, 3, device=dev, dtype=torch.float32)
+        depth = torch.empty(N, device=dev, dtype=torch.float32)
+        acc = torch.empty(N, device=dev, dtype=torch.float32)
+        dist = totals = None
+        if inv_range is not None:
+            dist = torch.empty(N, device=dev, dtype=torch.float32)
+            totals = torch.empty(N, 2, device=dev, dtype=torch.float64)
+        args = (ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step), ctx.step_size, ctx.white,
                 ptr(rgb), ptr(depth), ptr(acc), ptr(t_shift))
+        if any(ctx.variant):  # (the dist and bg entry points; the bg one takes both, either may be null)
+            args += (ctx.inv_range or 0.0, ptr(dist), ptr(totals))
         if bg is not None:
-            dist = totals = None
-            if inv_range is not None:
-                dist = torch.empty(N, device=dev, dtype=torch.float32)
-                totals = torch.empty(N, 2, device=dev, dtype=torch.float64)
-            # bytes: as below, and the colour 12 B read per ray
-            with kernel_timer("march_seg_composite_fwd_bg", 20 * M + (60 if dist is None else 80) * N, detail=True):
-                check(lib().nerf_march_seg_composite_fwd_bg(*head, ctx.inv_range or 0.0, ptr(dist), ptr(totals),
-                                                            ptr(bg), stream_of(rays)),
-                      "nerf_march_seg_composite_fwd_bg")
-            ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift, totals, bg)
-            return (rgb, depth, acc) if dist is None else (rgb, depth, acc, dist)
-        if inv_range is None:
-            # bytes: raw 16 B + step 4 B per point; ray 24 B, offsets 4 B, rgb/depth/acc 20 B per ray
-            with kernel_timer("march_seg_composite_fwd", 20 * M + 48 * N, detail=True):
-                check(lib().nerf_march_seg_composite_fwd_shift(*head, stream_of(rays)),
-                      "nerf_march_seg_composite_fwd")
-            ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift)
-            return rgb, depth, acc
-        dist = torch.empty(N, device=dev, dtype=torch.float32)
-        totals = torch.empty(N, 2, device=dev, dtype=torch.float64)
-        # bytes: the above, and dist 4 B + the totals 16 B written per ray
-        with kernel_timer("march_seg_composite_fwd_dist", 20 * M + 68 * N, detail=True):
-            check(lib().nerf_march_seg_composite_fwd_dist(*head, ctx.inv_range, ptr(dist), ptr(totals),
-                                                          stream_of(rays)), "nerf_march_seg_composite_fwd_dist")
-        ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift, totals)
-        return rgb, depth, acc, dist
+            args += (ptr(bg),)
+        with kernel_timer(f"march_seg_composite_fwd{label}", 20 * M + ray_bytes * N, detail=True):
+            check(getattr(lib(), fwd)(*args, stream_of(rays)), f"nerf_march_seg_composite_fwd{label}")
+        ctx.save_for_backward(raw, rays, t_table, seg_off, out_step, t_shift, totals, bg)
+        return (rgb, depth, acc) if dist is None else (rgb, depth, acc, dist)
 
     @staticmethod
     def backward(ctx, *grads):
         if all(t is None for t in grads):
             return (None,) * 10
-        raw, rays, t_table, seg_off, out_step, t_shift = ctx.saved_tensors[:6]
+        raw, rays, t_table, seg_off, out_step, t_shift, totals, bg = ctx.saved_tensors
         N, M = rays.shape[0], raw.shape[0]
+        _, bwd, label, ray_bytes = _SEG_COMPOSITE[ctx.variant]
         g = [None if t is None else _f32c(t, "cotangent") for t in grads]
         g_raw = torch.empty_like(raw)
-        head = (ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step), ctx.step_size, ctx.white,
+        args = (ptr(raw), ptr(rays), N, ptr(t_table), ptr(seg_off), ptr(out_step), ctx.step_size, ctx.white,
                 ptr(g[0]), ptr(g[1]), ptr(g[2]))
-        if len(ctx.saved_tensors) == 8:  # (a colour per ray)
-            totals, bg = ctx.saved_tensors[6:]
-            with kernel_timer("march_seg_composite_bwd_bg", 56 * M + (60 if totals is None else 80) * N, detail=True):
-                check(lib().nerf_march_seg_composite_bwd_bg(*head, ptr(t_shift), ctx.inv_range or 0.0,
-                                                            ptr(g[3]) if totals is not None else None, ptr(totals),
-                                                            ptr(g_raw), ptr(bg), stream_of(rays)),
-                      "nerf_march_seg_composite_bwd_bg")
-            return (g_raw,) + (None,) * 9
-        if ctx.inv_range is None:
-            # bytes: raw 16 B + step 4 B read twice (entry transmittances, then the reverse walk), d_raw 16 B written
-            with kernel_timer("march_seg_composite_bwd", 56 * M + 48 * N, detail=True):
-                check(lib().nerf_march_seg_composite_bwd_shift(*head, ptr(g_raw), ptr(t_shift), stream_of(rays)),
-                      "nerf_march_seg_composite_bwd")
-            return (g_raw,) + (None,) * 9
-        totals = ctx.saved_tensors[6]
-        # bytes: the above, and the cotangent of dist 4 B + the totals 16 B read per ray
-        with kernel_timer("march_seg_composite_bwd_dist", 56 * M + 68 * N, detail=True):
-            check(lib().nerf_march_seg_composite_bwd_dist(*head, ptr(t_shift), ctx.inv_range, ptr(g[3]),
-                                                          ptr(totals), ptr(g_raw), stream_of(rays)),
-                  "nerf_march_seg_composite_bwd_dist")
+        if not any(ctx.variant):
+            args += (ptr(g_raw), ptr(t_shift))
+        else:  # (the cotangent of dist: only the distortion variants return that map)
+            args += (ptr(t_shift), ctx.inv_range or 0.0, ptr(g[3]) if ctx.variant[1] else None, ptr(totals),
+                     ptr(g_raw))
+        if bg is not None:
+            args += (ptr(bg),)
+        with kernel_timer(f"march_seg_composite_bwd{label}", 56 * M + ray_bytes * N, detail=True):
+            check(getattr(lib(), bwd)(*args, stream_of(rays)), f"nerf_march_seg_composite_bwd{label}")
         return (g_raw,) + (None,) * 9
 
 
@@ -1160,7 +1143,7 @@ def march_segments(rays: torch.Tensor, t_table: torch.Tensor, grid_u8: torch.Ten
     (nerf_march_segments) -> out_ray [M] int32, out_step [M] int32 (-1: surplus), out_pts [M,3].
     ``t_shift`` (float32 [N]): ray r walks the depths t_table + t_shift[r]."""
     dev, N = rays.device, rays.shape[0]
-    t_shift = _shift_arg(t_shift, rays)
+    t_shift = _per_ray_arg(t_shift, rays, "t_shift", (), "shift")
     out_ray = torch.empty(M, dtype=torch.int32, device=dev)
     out_step = torch.empty(M, dtype=torch.int32, device=dev)
     out_pts = torch.empty(M, 3, device=dev)
@@ -1231,7 +1214,9 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
     (1 - acc[r]) bg[r] (nerf_march_seg_composite_fwd_bg / _bwd_bg).  Pass A never reads it
     (termination depends on the transmittance alone), so n_queried, depth and acc keep their bits;
     under ``max_points`` pass B reads bg[:rays_kept] and rows >= rays_kept keep pass A's values."""
-    bg = _bg_arg(bg, rays)
+    given = locals()
+    walk_opts = {k: given[k] for k in _WALK_OPTIONS}  # (as the caller gave them)
+    bg = _per_ray_arg(bg, rays, "bg", (3,), "colour")
     if distortion and not float(far) > float(near):
         raise ValueError(f"march_grad: distortion needs far > near, got near {near}, far {far}")
     if max_points is not None:
@@ -1242,10 +1227,7 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
             raise ValueError(f"march_grad: max_points must be in [{n_steps} (the march's steps: one ray can need "
                              f"them all), 2^31 - 1], got {max_points}")
     with torch.no_grad():
-        out, walk = _march(packer, rays, near, far, grid, step_size=step_size, t_thresh=t_thresh, bbox=bbox,
-                           white_bkgd=white_bkgd, dtype=dtype, t_table=t_table, k_schedule=k_schedule,
-                           round_bytes=round_bytes, use_macro=use_macro, return_used=True, budget=max_points,
-                           t_shift=t_shift)
+        out, walk = _march(packer, rays, near, far, grid, **walk_opts, return_used=True, budget=max_points)
     used = out.pop("ray_used")
     seg_off = out.pop("seg_off", None)
     if walk is None:  # no rays
@@ -1266,15 +1248,12 @@ def march_grad(packer: PackedMLP, rays: torch.Tensor, near: float, far: float, g
         bg = None if bg is None else bg[:n_keep]
     out_ray, out_step, out_pts = march_segments(rays_c, t_tab, g8, macro, seg_off, M, bbox, t_shift)
     raw = mlp(packer, out_pts, vd, 1, out_ray, dtype)
-    if distortion:
-        maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd),
-                                        t_shift, 1.0 / (float(far) - float(near)), bg)
-        out["dist_map_f"] = maps[3] if n_keep == N else torch.cat([maps[3], maps[3].new_zeros(N - n_keep)], 0)
-    else:
-        maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd),
-                                        t_shift, None, bg)
-    for k, v in zip(("rgb_map_f", "depth_map_f", "acc_map_f"), maps):
-        out[k] = v if n_keep == N else torch.cat([v, out[k][n_keep:]], 0)  # (the dropped rows: pass A's, no graph)
+    maps = _MarchSegComposite.apply(raw, rays_c, t_tab, seg_off, out_step, float(step_size), bool(white_bkgd),
+                                    t_shift, 1.0 / (float(far) - float(near)) if distortion else None, bg)
+    for k, v in zip(("rgb_map_f", "depth_map_f", "acc_map_f", "dist_map_f"), maps):  # (three maps, or all four)
+        if n_keep < N:  # the dropped rows: pass A's, no graph (the distortion is pass B's alone: zeros)
+            v = torch.cat([v, out[k][n_keep:] if k in out else v.new_zeros(N - n_keep)], 0)
+        out[k] = v
     return out
 
 

@@ -207,29 +207,28 @@ class Renderer:
         self.set_occupancy_grid(grid, device)
         print("Occupancy grid loaded and ready for accelerated rendering.")
 
+    def _install_grid(self, grid):
+        """``grid`` (on its device) as the march's grid, with the reference's attributes derived from it."""
+        device = grid.device
+        self.occupancy_grid = grid
+        self.grid_resolution = torch.tensor(grid.shape, device=device)
+        self.resolution = int(grid.shape[0])
+        self.scene_bbox = torch.tensor(cfg.train_dataset.scene_bbox, device=device, dtype=torch.float32)
+        self.voxel_size = (self.scene_bbox[1] - self.scene_bbox[0]) / self.grid_resolution
+
     def set_occupancy_grid(self, grid, device=None):
         device = device or torch.device("cuda", torch.cuda.current_device())
         if grid.dtype != torch.bool or grid.dim() != 3:
             raise ValueError("occupancy grid must be a 3-D bool tensor")
-        self.occupancy_grid = grid.to(device)
-        self.grid_resolution = torch.tensor(self.occupancy_grid.shape, device=device)
-        self.resolution = int(grid.shape[0])
-        self.scene_bbox = torch.tensor(cfg.train_dataset.scene_bbox, device=device, dtype=torch.float32)
-        self.voxel_size = (self.scene_bbox[1] - self.scene_bbox[0]) / self.grid_resolution
+        self._install_grid(grid.to(device))
 
     def set_live_grid(self, grid_u8):
         """The trainer's own grid (OnlineGrid.grid: uint8 [res,res,res] on the device, rewritten in place
         by its updates), taken as it is -- the march reads uint8, so no conversion per step."""
         if grid_u8.dtype != torch.uint8 or grid_u8.dim() != 3 or not grid_u8.is_contiguous():
             raise ValueError("the live occupancy grid must be a contiguous 3-D uint8 tensor")
-        if self.occupancy_grid is grid_u8:
-            return
-        device = grid_u8.device
-        self.occupancy_grid = grid_u8
-        self.grid_resolution = torch.tensor(grid_u8.shape, device=device)
-        self.resolution = int(grid_u8.shape[0])
-        self.scene_bbox = torch.tensor(cfg.train_dataset.scene_bbox, device=device, dtype=torch.float32)
-        self.voxel_size = (self.scene_bbox[1] - self.scene_bbox[0]) / self.grid_resolution
+        if self.occupancy_grid is not grid_u8:
+            self._install_grid(grid_u8)
 
     def _bbox_tuple(self):
         b = cfg.train_dataset.scene_bbox
@@ -265,39 +264,32 @@ class Renderer:
                              "train dataset adds under this key)")
         else:
             bg = bg.reshape(-1, 3)
-        distortion = distortion_loss_setting(ta) > 0.0
         start = time.time()
-        chunk = self._chunk(True)
-        packer = self.net.model_fine.packer()
-        sched = tuple(int(k) for k in ta.get("train_k_schedule", TRAIN_K_SCHEDULE))
+        n = rays_flat.shape[0]
         t_shift = None
         if march_jitter_setting(ta):
             off, _ = self._next_offsets()
-            t_shift = ops.march_jitter(rays_flat.shape[0], float(ta.render_step_size), self._seed, off,
-                                       rays_flat.device)
-        if self.max_points:
-            out = ops.march_grad(packer, rays_flat, near, far, self.occupancy_grid,
-                                 step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
-                                 bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
-                                 k_schedule=sched, max_points=int(self.max_points), t_shift=t_shift,
-                                 distortion=distortion, bg=bg)
-            keys = ("rgb_map_f", "depth_map_f", "acc_map_f", "n_queried", "n_evaluated", "rounds", "rays_kept",
-                    "n_points") + (("dist_map_f",) if distortion else ())
-            ret = {k: out[k] for k in keys}
-            ret["render_time"] = time.time() - start
-            if t_shift is not None:
-                ret["t_shift"] = t_shift
-            return ret
-        maps = {"rgb_map_f": [], "depth_map_f": [], "acc_map_f": []}
-        if distortion:
+            t_shift = ops.march_jitter(n, float(ta.render_step_size), self._seed, off, rays_flat.device)
+        kw = dict(step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
+                  bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
+                  k_schedule=tuple(int(k) for k in ta.get("train_k_schedule", TRAIN_K_SCHEDULE)),
+                  distortion=distortion_loss_setting(ta) > 0.0)
+        maps = {k: [] for k in ("rgb_map_f", "depth_map_f", "acc_map_f")}
+        if kw["distortion"]:
             maps["dist_map_f"] = []
         counts = {"n_queried": 0, "n_evaluated": 0, "rounds": 0}
-        for i in range(0, rays_flat.shape[0], chunk):
-            out = ops.march_grad(packer, rays_flat[i:i + chunk], near, far, self.occupancy_grid,
-                                 step_size=float(ta.render_step_size), t_thresh=float(ta.transmittance_threshold),
-                                 bbox=self._bbox_tuple(), white_bkgd=bool(ta.white_bkgd), dtype=self.net.mlp_dtype,
-                                 k_schedule=sched, t_shift=None if t_shift is None else t_shift[i:i + chunk],
-                                 distortion=distortion, bg=None if bg is None else bg[i:i + chunk])
+        if self.max_points:  # one span, the whole batch, capped
+            kw["max_points"] = int(self.max_points)
+            counts.update(rays_kept=0, n_points=0)
+            spans = [slice(0, n)]
+        else:
+            chunk = self._chunk(True)
+            spans = [slice(i, i + chunk) for i in range(0, n, chunk)]
+        packer = self.net.model_fine.packer()
+        for sp in spans:
+            out = ops.march_grad(packer, rays_flat[sp], near, far, self.occupancy_grid,
+                                 t_shift=None if t_shift is None else t_shift[sp],
+                                 bg=None if bg is None else bg[sp], **kw)
             for k, v in maps.items():
                 v.append(out[k])
             for k in counts:

@@ -205,14 +205,9 @@ class NetworkWrapper(nn.Module):
                 grid.step(fine.packer(), self.net.mlp_dtype)  # (may update; update 0 precedes the first march)
             elif grid.updates == 0:  # validation before any training step: never march the all-ones grid
                 grid.update(fine.packer(), self.net.mlp_dtype)
-            if budgeted:
-                return self._budgeted_step(batch, gt)
-            ret = self.renderer.render_accelerated(batch)
-            total, stats = self._march_loss(ret, gt)
-            return ret, total, stats
         if budgeted:
             return self._budgeted_step(batch, gt)
-        if self.train_renderer == "accelerated" and torch.is_grad_enabled():
+        if self.online_grid is not None or (self.train_renderer == "accelerated" and torch.is_grad_enabled()):
             # the fine net through the grid march; the MSE and its backward in one launch each
             # (ops.mse_pair with no second image)
             ret = self.renderer.render_accelerated(batch)

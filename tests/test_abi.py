@@ -5,6 +5,8 @@ import re
 
 import pytest
 
+from march_support import lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "nerf_amd.h")
 
@@ -13,14 +15,6 @@ def declared_functions():
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(nerf_[a-z0-9_]+)\s*\(", text)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from nerf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("library not built (run __graft_entry__.build())")
-    return _lib.lib()
 
 
 def test_header_declares_the_hot_path():

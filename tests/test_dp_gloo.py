@@ -7,20 +7,13 @@ with the mean; broadcast_params must give every rank rank-0's weights
 tile-split renderer must reproduce a single-process render.
 """
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from march_support import _free_port
 
 
 class _FakeRenderer:

@@ -3,19 +3,12 @@
 only its bucket fires from the backward; GradBuckets.finish must all-reduce the coarse range
 too (zero on every rank) and leave every rank with the average of the flat gradient."""
 import os
-import socket
 
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+from march_support import _free_port
 
 
 def _worker(rank, world, port, q):

@@ -16,7 +16,6 @@ batch.  Asserted:
     step waits for the all-reduce) trains exactly like the plain one (test_prefetch_*).
 """
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -24,17 +23,11 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from march_support import _free_port
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _setup(dtype, seed_images=7):

@@ -6,7 +6,6 @@ the counts may differ between the ranks; the gradient all-reduce averages the ra
 so after every step the weights are bit-identical, and with them the online grids.
 """
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -14,19 +13,13 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from march_support import _free_port
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 STEPS = 3
 TARGET, CAP, MIN_RAYS = 32768, 49152, 256
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _formula(n_rays, n_queried):

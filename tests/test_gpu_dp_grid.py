@@ -7,7 +7,6 @@ weights), with no collective of its own.  After 2 * interval + 1 steps (three up
 rolling) the densities, the occupancies and the weights are bit-equal across the ranks.
 """
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -15,18 +14,12 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from march_support import _free_port
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 INTERVAL = 4
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, q):

@@ -13,17 +13,13 @@ ReLU branches (round 6's wide forward did, 5.6e-7 of them)."""
 import pytest
 import torch
 
+from march_support import ops
+
 pytestmark = pytest.mark.gpu
 
 MS = (1, 17, 131, 4099)
 SPDS = (7, 192)
 WIDE, NARROW = 1, 5  # nerf_mlp_fwd flags: NERF_MLP_STORE, NERF_MLP_STORE | NERF_MLP_F32_NARROW
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from nerf_amd import ops
-    return ops
 
 
 def _inputs(M, spd):

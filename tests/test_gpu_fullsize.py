@@ -17,24 +17,14 @@ import numpy as np
 import pytest
 import torch
 
+from march_support import O, ops
+
 pytestmark = pytest.mark.gpu
 
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
 
 H = W = 800
 CAM_X = 0.6911112070083618  # lego camera_angle_x (blender.py:74-75)
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import nerf_oracle
-    return nerf_oracle
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from nerf_amd import ops
-    return ops
 
 
 @pytest.fixture(scope="module")

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from march_support import _batch, fp32_cfg, g2
+
 pytestmark = pytest.mark.gpu
 
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
@@ -16,11 +18,6 @@ LEGO = ((-1.5, -1.5, -1.5), (1.5, 1.5, 1.5))
 SKEW = ((-1.3, -0.4, 0.1), (0.7, 1.9, 2.3))
 BBOXES = {"lego": LEGO, "skew": SKEW}
 RES = [2, 8, 33, 128]
-
-
-@pytest.fixture(scope="module")
-def g2():
-    return np.load(os.path.join(HERE, "golden", "golden_v2.npz"), allow_pickle=False)
 
 
 @pytest.fixture(scope="module")
@@ -36,19 +33,8 @@ def _trained_state():
 @pytest.fixture()
 def online_cfg():
     """cfg with the keys the tests below set restored afterwards."""
-    from src.config import cfg
-    ta = cfg.task_arg
-    keys = ("train_renderer", "train_grid", "grid_update", "mlp_dtype", "perturb", "train_rays", "occupancy_grid_res",
-            "occupancy_grid_threshold", "chunk_size")
-    old = {k: ta[k] for k in keys if k in ta}
-    ta.perturb = 0
-    ta.mlp_dtype = "fp32"
-    yield cfg
-    for k in keys:
-        if k in old:
-            ta[k] = old[k]
-        else:
-            ta.pop(k, None)
+    yield from fp32_cfg(("train_renderer", "train_grid", "grid_update", "mlp_dtype", "perturb", "train_rays",
+                         "occupancy_grid_res", "occupancy_grid_threshold", "chunk_size"))
 
 
 def _net(cuda, state=None):
@@ -68,15 +54,6 @@ def trained(cuda, online_cfg):
 def _cell_ijk(cells, res):
     c = cells.long()
     return torch.stack([c // (res * res), (c // res) % res, c % res], 1)
-
-
-def _batch(rays, cuda, rgbs=None):
-    from nerf_amd import ops
-    b = {"rays": torch.as_tensor(rays).to(cuda)[None], "near": ops.device_scalar(2.0, cuda),
-         "far": ops.device_scalar(6.0, cuda)}
-    if rgbs is not None:
-        b["rgbs"] = torch.as_tensor(rgbs).to(cuda)[None]
-    return b
 
 
 # --------------------------------------------------------------------------------------
@@ -287,7 +264,7 @@ def test_step_equals_the_file_mode_step(cuda, trained, g2, tmp_path, monkeypatch
     cfg, net = trained
     monkeypatch.chdir(tmp_path)
     gt = torch.rand(256, 3, generator=torch.Generator().manual_seed(1))
-    batch = _batch(g2["march_rays"], cuda, gt)
+    batch = _batch(g2["march_rays"], cuda, gt, device_scalar=True)
     cfg.task_arg.train_renderer = "accelerated"
     cfg.task_arg.train_grid = "online"
     online = make_trainer(cfg, net)
@@ -402,7 +379,7 @@ def test_save_and_load(cuda, trained, g2, tmp_path, monkeypatch):
     ta.occupancy_grid_res = 33
     ta.grid_update = {"interval": 2, "warmup_updates": 1, "period": 4}
     gt = torch.rand(256, 3, generator=torch.Generator().manual_seed(1))
-    batch = _batch(g2["march_rays"], cuda, gt)
+    batch = _batch(g2["march_rays"], cuda, gt, device_scalar=True)
     a = make_trainer(cfg, net)
     opt = make_optimizer(cfg, net)
     for _ in range(3):  # updates at the grid's steps 0 (full) and 2 (rolling)

@@ -7,23 +7,13 @@ import numpy as np
 import pytest
 import torch
 
+from march_support import O, ops
+
 pytestmark = pytest.mark.gpu
 
 
 def _t(x, dev):
     return torch.from_numpy(np.asarray(x)).to(dev)
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import nerf_oracle
-    return nerf_oracle
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from nerf_amd import ops
-    return ops
 
 
 @pytest.fixture(scope="module")

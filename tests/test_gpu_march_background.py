@@ -5,9 +5,9 @@ instantiations of the segment compositing kernels (nerf_march_seg_composite_fwd_
 prediction onto the same colour:  rgb_r = sum_k w_k c_k + (1 - acc_r) bg_r,  g_acc' = g_acc - g_rgb . bg_r.
 
 Checked here: the ray generation against nerf_raygen and a numpy Philox / blend, bit for bit; the kernels
-against fp64 (the segment case of test_gpu_march_distortion.py: segments that cross the backward's 64-chunk
-register window, alpha == 1 points, surplus tails), with and without the distortion term and the per-ray
-shift; the identities with the white / black entry points, bit for bit; that a white floater in front of a
+against fp64 (march_support's long-segment case, test_gpu_march_distortion.py's too: segments that cross the
+backward's 64-chunk register window, alpha == 1 points, surplus tails), with and without the distortion term and
+the per-ray shift; the identities with the white / black entry points, bit for bit; that a white floater in front of a
 transparent pixel gets a density gradient (the point of the key); ops.march_grad(bg=) on the trained fixture
 net; the renderer, the dataset and the trainer; and that a step trains.
 """
@@ -17,15 +17,13 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_march_distortion import (ALPHA_ONE, INV_RANGE, LONG, STEP, _dist_double_sum, _dist_prefix,
-                                       _per_segment_bound, _segment_case)
-from test_march_background_cpu import blend_f32
+from march_support import (ALPHA_ONE, INV_RANGE, LONG, MAPS, STEP, _batch, _dist_double_sum, _dist_prefix, _flat_grad,
+                           _march_grad, _per_segment_bound, _trained_net, _trainer, _write_grid, blend_f32, fp32_cfg,
+                           g2, long_segment_case, trained_grid)
 
 pytestmark = pytest.mark.gpu
 
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
-HERE = os.path.dirname(os.path.abspath(__file__))
-MAPS = ("rgb_map_f", "depth_map_f", "acc_map_f")
 KEY = "train_background"
 
 
@@ -174,7 +172,7 @@ def _reference(c, bg, t_shift):
 
 @pytest.fixture(scope="module")
 def segment_case():
-    c = _segment_case()
+    c = long_segment_case()
     assert c["lens"][BLACK] == 65 and c["lens"][WHITE] == 800
     c["bg"], c["shift"] = _colours(c["N"]), _shifts(c["N"])
     c["ref"] = {s: _reference(c, c["bg"], c["shift"] if s else None) for s in (False, True)}  # computed once, shared
@@ -366,41 +364,11 @@ def test_white_floater_gets_a_gradient(cuda):
 # --------------------------------------------------------------------------------------
 # 5. ops.march_grad(bg=) on the trained fixture net and its own bake
 # --------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def g2():
-    return np.load(os.path.join(HERE, "golden", "golden_v2.npz"), allow_pickle=False)
-
-
-@pytest.fixture(scope="module")
-def trained_grid(g2):
-    return torch.from_numpy(np.unpackbits(g2["bake128_packed"])[: 128 ** 3].reshape(128, 128, 128).astype(bool))
-
-
-def _trained_net(cuda):
-    from src.models.nerf.network import Network
-    z = np.load(os.path.join(HERE, "golden", "trained_v2.npz"), allow_pickle=False)
-    torch.manual_seed(0)
-    net = Network()
-    net.load_state_dict({k: torch.from_numpy(z[k]) for k in z.files}, strict=True)
-    return net.to(cuda)
-
-
 @pytest.fixture()
 def bg_cfg():
     """cfg with the keys the tests below set restored afterwards."""
-    from src.config import cfg
-    ta = cfg.task_arg
-    keys = ("train_renderer", "train_grid", "point_budget", "mlp_dtype", "perturb", "chunk_size", "train_rays",
-            "distortion_loss_weight", "train_march_jitter", KEY)
-    old = {k: ta[k] for k in keys if k in ta}
-    ta.perturb = 0
-    ta.mlp_dtype = "fp32"
-    yield cfg
-    for k in keys:
-        if k in old:
-            ta[k] = old[k]
-        else:
-            ta.pop(k, None)
+    yield from fp32_cfg(("train_renderer", "train_grid", "point_budget", "mlp_dtype", "perturb", "chunk_size",
+                         "train_rays", "distortion_loss_weight", "train_march_jitter", "train_background"))
 
 
 @pytest.fixture()
@@ -415,20 +383,6 @@ def fixture_net(cuda, bg_cfg, g2, trained_grid):
     bg = torch.rand(256, 3, generator=torch.Generator().manual_seed(2)).to(cuda)
     return {"net": net, "opt": opt, "rays": rays, "t_table": t_table, "gt": gt, "bg": bg,
             "grid": trained_grid.to(cuda)}
-
-
-def _flat_grad(f, loss):
-    from nerf_amd import ops
-    f["opt"].zero_grad()
-    with ops.direct_grad():
-        loss.backward()
-    return f["opt"].flat_grad.clone()
-
-
-def _march_grad(f, rays, **kw):
-    from nerf_amd import ops
-    kw.setdefault("t_table", f["t_table"])
-    return ops.march_grad(f["net"].model_fine.packer(), rays, 2.0, 6.0, f["grid"], dtype="fp32", **kw)
 
 
 def test_march_grad_with_the_colours(cuda, fixture_net):
@@ -492,16 +446,6 @@ def test_march_grad_colours_under_the_point_budget(cuda, fixture_net):
 # --------------------------------------------------------------------------------------
 # 6. renderer, dataset, trainer
 # --------------------------------------------------------------------------------------
-def _batch(rays, cuda, rgbs=None, bg=None):
-    b = {"rays": torch.as_tensor(rays).to(cuda)[None], "near": torch.tensor([2.0], device=cuda),
-         "far": torch.tensor([6.0], device=cuda)}
-    if rgbs is not None:
-        b["rgbs"] = torch.as_tensor(rgbs).to(cuda)[None]
-    if bg is not None:
-        b["bg"] = torch.as_tensor(bg).to(cuda)[None]
-    return b
-
-
 def test_chunked_step_equals_unchunked(cuda, bg_cfg, g2, trained_grid):
     from src.models.nerf.renderer.volume_renderer import Renderer
     cfg = bg_cfg
@@ -565,22 +509,6 @@ def test_dataset_draws_colours(cuda, bg_cfg):
     it = test[1]
     assert "bg" not in it and test.images_rgba is None
     assert torch.equal(it["rgbs"][0], make_scene(4, 16, 16, cuda)[0][1].reshape(-1, 3))
-
-
-def _write_grid(tmp_path, monkeypatch, grid):
-    """logs/<cfg name>/occupancy_grid.pt under a temporary working directory."""
-    from src.config.config import args
-    monkeypatch.chdir(tmp_path)
-    d = tmp_path / "logs" / os.path.splitext(os.path.basename(args.cfg_file))[0]
-    d.mkdir(parents=True)
-    torch.save(grid, str(d / "occupancy_grid.pt"))
-
-
-def _trainer(cfg, cuda):
-    from src.train.optimizer import make_optimizer
-    from src.train.trainers.make_trainer import make_trainer
-    net = _trained_net(cuda)
-    return net, make_trainer(cfg, net), make_optimizer(cfg, net)
 
 
 def test_trainer_key_on_off_and_validation(cuda, bg_cfg, g2, trained_grid, tmp_path, monkeypatch):

@@ -8,11 +8,12 @@ import numpy as np
 import pytest
 import torch
 
+from march_support import (MAPS, _batch, _flat_grad, _loss, _march_grad, _trained_net, _write_grid, fixture_net,
+                           fp32_cfg, g2, trained_grid)
+
 pytestmark = pytest.mark.gpu
 
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
-HERE = os.path.dirname(os.path.abspath(__file__))
-MAPS = ("rgb_map_f", "depth_map_f", "acc_map_f")
 INT32_MAX = 2 ** 31 - 1
 
 
@@ -23,50 +24,11 @@ def formula(n_rays, n_queried, target, min_rays=1024, max_rays=32768, granularit
     return min(max((want // granularity) * granularity, min_rays), max_rays)
 
 
-@pytest.fixture(scope="module")
-def g2():
-    return np.load(os.path.join(HERE, "golden", "golden_v2.npz"), allow_pickle=False)
-
-
-@pytest.fixture(scope="module")
-def trained_grid(g2):
-    return torch.from_numpy(np.unpackbits(g2["bake128_packed"])[: 128 ** 3].reshape(128, 128, 128).astype(bool))
-
-
 @pytest.fixture()
 def budget_cfg():
     """cfg with the keys the tests below set restored afterwards."""
-    from src.config import cfg
-    ta = cfg.task_arg
-    keys = ("train_renderer", "train_grid", "grid_update", "point_budget", "mlp_dtype", "perturb", "train_rays",
-            "occupancy_grid_res", "occupancy_grid_threshold", "chunk_size")
-    old = {k: ta[k] for k in keys if k in ta}
-    ta.perturb = 0
-    ta.mlp_dtype = "fp32"
-    yield cfg
-    for k in keys:
-        if k in old:
-            ta[k] = old[k]
-        else:
-            ta.pop(k, None)
-
-
-def _trained_net(cuda):
-    from src.models.nerf.network import Network
-    z = np.load(os.path.join(HERE, "golden", "trained_v2.npz"), allow_pickle=False)
-    torch.manual_seed(0)
-    net = Network()
-    net.load_state_dict({k: torch.from_numpy(z[k]) for k in z.files}, strict=True)
-    return net.to(cuda)
-
-
-def _batch(rays, cuda, rgbs=None):
-    from nerf_amd import ops
-    b = {"rays": torch.as_tensor(rays).to(cuda)[None], "near": ops.device_scalar(2.0, cuda),
-         "far": ops.device_scalar(6.0, cuda)}
-    if rgbs is not None:
-        b["rgbs"] = torch.as_tensor(rgbs).to(cuda)[None]
-    return b
+    yield from fp32_cfg(("train_renderer", "train_grid", "grid_update", "point_budget", "mlp_dtype", "perturb",
+                         "train_rays", "occupancy_grid_res", "occupancy_grid_threshold", "chunk_size"))
 
 
 # --------------------------------------------------------------------------------------
@@ -163,44 +125,6 @@ def test_budget_kernel_writes_into_spare_slots(cuda):
 # --------------------------------------------------------------------------------------
 # 2. march_grad(max_points=) on the trained fixture net and its own bake
 # --------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def fixture_net(cuda, g2, trained_grid):
-    """The trained fixture net, its optimizer (the flat gradient), the 256 march rays, a ground truth."""
-    from src.config import cfg
-    from src.train.optimizer import make_optimizer
-    old = {k: cfg.task_arg[k] for k in ("perturb", "mlp_dtype")}
-    cfg.task_arg.perturb = 0
-    cfg.task_arg.mlp_dtype = "fp32"
-    net = _trained_net(cuda)
-    opt = make_optimizer(cfg, net)
-    rays = torch.from_numpy(g2["march_rays"]).to(cuda)
-    t_table = torch.from_numpy(g2["march_t_table"]).to(cuda)
-    gt = torch.rand(256, 3, generator=torch.Generator().manual_seed(1)).to(cuda)
-    yield {"net": net, "opt": opt, "rays": rays, "t_table": t_table, "gt": gt, "grid": trained_grid.to(cuda)}
-    for k, v in old.items():
-        cfg.task_arg[k] = v
-
-
-def _loss(out, gt, rows=None):
-    rgb, depth, acc = (out[m] if rows is None else out[m][:rows] for m in MAPS)
-    gt = gt if rows is None else gt[:rows]
-    return torch.nn.functional.mse_loss(rgb, gt) + 0.1 * depth.mean() + 0.1 * acc.mean()
-
-
-def _flat_grad(f, loss):
-    from nerf_amd import ops
-    f["opt"].zero_grad()
-    with ops.direct_grad():
-        loss.backward()
-    return f["opt"].flat_grad.clone()
-
-
-def _march_grad(f, rays, dtype, **kw):
-    from nerf_amd import ops
-    return ops.march_grad(f["net"].model_fine.packer(), rays, 2.0, 6.0, f["grid"], t_table=f["t_table"], dtype=dtype,
-                          **kw)
-
-
 def test_a_cap_above_everything_changes_nothing(cuda, fixture_net):
     f = fixture_net
     plain = _march_grad(f, f["rays"], "fp32")
@@ -261,15 +185,6 @@ def test_a_cap_below_the_steps_is_refused(cuda, fixture_net):
 # --------------------------------------------------------------------------------------
 # 3. the budgeted training step
 # --------------------------------------------------------------------------------------
-def _write_grid(tmp_path, monkeypatch, grid):
-    """logs/<cfg name>/occupancy_grid.pt under a temporary working directory."""
-    from src.config.config import args
-    monkeypatch.chdir(tmp_path)
-    d = tmp_path / "logs" / os.path.splitext(os.path.basename(args.cfg_file))[0]
-    d.mkdir(parents=True)
-    torch.save(grid, str(d / "occupancy_grid.pt"))
-
-
 def test_training_step_with_a_budget(cuda, budget_cfg, g2, trained_grid, tmp_path, monkeypatch):
     from src.train.optimizer import make_optimizer
     from src.train.trainers.make_trainer import make_trainer
@@ -281,7 +196,7 @@ def test_training_step_with_a_budget(cuda, budget_cfg, g2, trained_grid, tmp_pat
     ta.train_grid = "file"
     ta.point_budget = {"target": 8192, "max_points": 4096}
     gt = torch.rand(256, 3, generator=torch.Generator().manual_seed(1))
-    batch = _batch(g2["march_rays"], cuda, gt)
+    batch = _batch(g2["march_rays"], cuda, gt, device_scalar=True)
     trainer = make_trainer(cfg, net)
     budget = trainer.network.ray_budget
     assert budget.rays == 4096 and budget.max_points == 4096 and trainer.network.online_grid is None
@@ -444,7 +359,7 @@ def test_save_and_resume(cuda, budget_cfg, g2, tmp_path, monkeypatch):
     ta.grid_update = {"interval": 2, "warmup_updates": 1, "period": 4}
     ta.point_budget = {"target": 8192, "max_points": 4096}
     gt = torch.rand(256, 3, generator=torch.Generator().manual_seed(1))
-    batch = _batch(g2["march_rays"], cuda, gt)
+    batch = _batch(g2["march_rays"], cuda, gt, device_scalar=True)
     a = make_trainer(cfg, net)
     opt = make_optimizer(cfg, net)
     assert a.network.ray_budget.rays == 2048

@@ -15,61 +15,18 @@ import numpy as np
 import pytest
 import torch
 
+from march_support import (ALPHA_ONE, INV_RANGE, LONG, MAPS, STEP, _dist_double_sum, _dist_prefix, _flat_grad,
+                           _march_grad, _per_segment_bound, _trained_net, _write_grid, fp32_cfg, g2,
+                           long_segment_case, trained_grid)
+
 pytestmark = pytest.mark.gpu
 
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
-HERE = os.path.dirname(os.path.abspath(__file__))
-MAPS = ("rgb_map_f", "depth_map_f", "acc_map_f")
-STEP = 0.005
-INV_RANGE = 0.25  # near 2, far 6
 
 
 # --------------------------------------------------------------------------------------
 # 1. against the definition in fp64
 # --------------------------------------------------------------------------------------
-SEG_LENGTHS = [0, 1, 2, 63, 64, 65, 128, 129, 800, 4097, 4160]
-LONG = (9, 10)                                # the segments past the backward's 64-chunk register window
-ALPHA_ONE = [(8, 200), (10, 4100), (7, 64)]   # (segment, position): raw[3] = 1e4 -> alpha is exactly 1
-SURPLUS = {6: 1, 7: 5}                        # segment -> length of its -1 tail
-N_SEG = 23
-N_TABLE = 5000
-
-
-def _segment_case():
-    g = torch.Generator().manual_seed(5)
-    lens = SEG_LENGTHS + torch.randint(0, 201, (N_SEG - len(SEG_LENGTHS),), generator=g).tolist()
-    steps = []
-    for i, n in enumerate(lens):
-        s = torch.randperm(N_TABLE, generator=g)[:n].sort().values.to(torch.int32)  # strictly increasing
-        if i in SURPLUS:
-            s[n - SURPLUS[i]:] = -1
-        steps.append(s)
-    seg_off = torch.tensor([0] + np.cumsum(lens).tolist(), dtype=torch.int32)
-    M = int(seg_off[-1])
-    raw = torch.randn(M, 4, generator=g)
-    raw[:, :3] *= 2.0
-    for i in range(N_SEG):  # sigma logits: x4 on half of the segments (the weights spread along the ray), x40 on the rest
-        raw[int(seg_off[i]):int(seg_off[i + 1]), 3] *= 4.0 if i % 2 == 0 else 40.0
-    for seg, pos in ALPHA_ONE:
-        raw[int(seg_off[seg]) + pos, 3] = 1e4
-    rays = torch.cat([torch.randn(N_SEG, 3, generator=g), torch.randn(N_SEG, 3, generator=g)], 1)
-    cot = (torch.randn(N_SEG, 3, generator=g), torch.randn(N_SEG, generator=g), torch.randn(N_SEG, generator=g),
-           torch.randn(N_SEG, generator=g))
-    t_table = (2.0 + 0.005 * torch.arange(N_TABLE, dtype=torch.float64)).float()
-    return dict(N=N_SEG, lens=lens, seg_off=seg_off, out_step=torch.cat(steps), raw=raw, rays=rays, cot=cot,
-                t_table=t_table)
-
-
-def _dist_double_sum(w, t):
-    return INV_RANGE * ((w[:, None] * w[None, :] * (t[:, None] - t[None, :]).abs()).sum() + STEP / 3.0 * (w * w).sum())
-
-
-def _dist_prefix(w, t):
-    wt = w * t
-    Wex, Sex = torch.cumsum(w, 0) - w, torch.cumsum(wt, 0) - wt
-    return INV_RANGE * (2.0 * (w * (t * Wex - Sex)).sum() + STEP / 3.0 * (w * w).sum())
-
-
 def _segment_reference(c, white):
     """fp64 on the CPU, out of place: the compositor of test_gpu_march_grad's reference, and the distortion by
     its O(n^2) definition -- by the prefix-sum form on the two long segments, after that form has been shown
@@ -117,7 +74,7 @@ def _segment_reference(c, white):
 
 @pytest.fixture(scope="module")
 def segment_case():
-    c = _segment_case()
+    c = long_segment_case()
     c["ref"] = {white: _segment_reference(c, white) for white in (False, True)}  # computed once, shared
     return c
 
@@ -132,20 +89,6 @@ def _apply(c, cuda, white, dist=True, t_shift=None, t_table=None):
     elif t_shift is not None:
         args += [t_shift]
     return raw, ops._MarchSegComposite.apply(*args)
-
-
-def _per_segment_bound(c, got, ref, what):
-    """every entry within 1e-4 of its segment's largest reference entry"""
-    off = c["seg_off"].tolist()
-    worst = 0.0
-    for r in range(c["N"]):
-        if off[r + 1] == off[r]:
-            continue
-        big = float(ref[off[r]:off[r + 1]].abs().max())
-        err = float((got[off[r]:off[r + 1]].double() - ref[off[r]:off[r + 1]]).abs().max())
-        worst = max(worst, err / big if big > 0 else (0.0 if err == 0 else float("inf")))
-        assert err <= 1e-4 * big, (what, r, c["lens"][r], err, big)
-    return worst
 
 
 @pytest.mark.parametrize("white", [False, True])
@@ -268,41 +211,11 @@ def test_a_constant_shift_is_the_shifted_table(cuda, segment_case):
 # --------------------------------------------------------------------------------------
 # 5. end to end: ops.march_grad(distortion=True) on the trained fixture net and its own bake
 # --------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def g2():
-    return np.load(os.path.join(HERE, "golden", "golden_v2.npz"), allow_pickle=False)
-
-
-@pytest.fixture(scope="module")
-def trained_grid(g2):
-    return torch.from_numpy(np.unpackbits(g2["bake128_packed"])[: 128 ** 3].reshape(128, 128, 128).astype(bool))
-
-
-def _trained_net(cuda):
-    from src.models.nerf.network import Network
-    z = np.load(os.path.join(HERE, "golden", "trained_v2.npz"), allow_pickle=False)
-    torch.manual_seed(0)
-    net = Network()
-    net.load_state_dict({k: torch.from_numpy(z[k]) for k in z.files}, strict=True)
-    return net.to(cuda)
-
-
 @pytest.fixture()
 def dist_cfg():
     """cfg with the keys the tests below set restored afterwards."""
-    from src.config import cfg
-    ta = cfg.task_arg
-    keys = ("train_renderer", "train_grid", "point_budget", "mlp_dtype", "perturb", "chunk_size", "train_rays",
-            "distortion_loss_weight")
-    old = {k: ta[k] for k in keys if k in ta}
-    ta.perturb = 0
-    ta.mlp_dtype = "fp32"
-    yield cfg
-    for k in keys:
-        if k in old:
-            ta[k] = old[k]
-        else:
-            ta.pop(k, None)
+    yield from fp32_cfg(("train_renderer", "train_grid", "point_budget", "mlp_dtype", "perturb", "chunk_size",
+                         "train_rays", "distortion_loss_weight"))
 
 
 @pytest.fixture()
@@ -315,20 +228,6 @@ def fixture_net(cuda, dist_cfg, g2, trained_grid):
     t_table = torch.from_numpy(g2["march_t_table"]).to(cuda)
     gt = torch.rand(256, 3, generator=torch.Generator().manual_seed(1)).to(cuda)
     return {"net": net, "opt": opt, "rays": rays, "t_table": t_table, "gt": gt, "grid": trained_grid.to(cuda)}
-
-
-def _flat_grad(f, loss):
-    from nerf_amd import ops
-    f["opt"].zero_grad()
-    with ops.direct_grad():
-        loss.backward()
-    return f["opt"].flat_grad.clone()
-
-
-def _march_grad(f, rays, **kw):
-    from nerf_amd import ops
-    kw.setdefault("t_table", f["t_table"])
-    return ops.march_grad(f["net"].model_fine.packer(), rays, 2.0, 6.0, f["grid"], dtype="fp32", **kw)
 
 
 def test_march_grad_with_the_map(cuda, fixture_net):
@@ -388,15 +287,6 @@ def test_chunks_and_the_point_budget(cuda, fixture_net, trained_grid):
 # --------------------------------------------------------------------------------------
 # 6. the training step
 # --------------------------------------------------------------------------------------
-def _write_grid(tmp_path, monkeypatch, grid):
-    """logs/<cfg name>/occupancy_grid.pt under a temporary working directory."""
-    from src.config.config import args
-    monkeypatch.chdir(tmp_path)
-    d = tmp_path / "logs" / os.path.splitext(os.path.basename(args.cfg_file))[0]
-    d.mkdir(parents=True)
-    torch.save(grid, str(d / "occupancy_grid.pt"))
-
-
 def test_training_step_with_the_loss(cuda, dist_cfg, g2, trained_grid, tmp_path, monkeypatch):
     from nerf_amd import ops
     from src.train.optimizer import make_optimizer

@@ -22,33 +22,12 @@ import numpy as np
 import pytest
 import torch
 
+from march_support import MAPS, _batch, _write_grid, g2, lego_grid, mg, trained_grid
+
 pytestmark = pytest.mark.gpu
 
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
 HERE = os.path.dirname(os.path.abspath(__file__))
-MAPS = ("rgb_map_f", "depth_map_f", "acc_map_f")
-
-
-@pytest.fixture(scope="module")
-def g2():
-    return np.load(os.path.join(HERE, "golden", "golden_v2.npz"), allow_pickle=False)
-
-
-@pytest.fixture(scope="module")
-def mg():
-    return np.load(os.path.join(HERE, "golden", "golden_march_grad.npz"), allow_pickle=False)
-
-
-@pytest.fixture(scope="module")
-def lego_grid():
-    z = np.load(os.path.join(HERE, "golden", "lego_occupancy_grid.npz"))
-    shape = tuple(int(v) for v in z["shape"])
-    return torch.from_numpy(np.unpackbits(z["packed"])[: int(np.prod(shape))].reshape(shape).astype(bool))
-
-
-@pytest.fixture(scope="module")
-def trained_grid(g2):
-    return torch.from_numpy(np.unpackbits(g2["bake128_packed"])[: 128 ** 3].reshape(128, 128, 128).astype(bool))
 
 
 def _net(state, cuda):
@@ -78,11 +57,6 @@ def trained(cuda):
 def seeded(cuda, seeded_state):
     from src.config import cfg
     return cfg, _net(seeded_state, cuda)
-
-
-def _batch(rays, cuda):
-    return {"rays": torch.as_tensor(rays).to(cuda)[None], "near": torch.tensor([2.0], device=cuda),
-            "far": torch.tensor([6.0], device=cuda)}
 
 
 # --------------------------------------------------------------------------------------
@@ -476,15 +450,6 @@ def test_chunked_equals_unchunked(g2, cuda, trained, trained_grid):
 # --------------------------------------------------------------------------------------
 # 9. the training step
 # --------------------------------------------------------------------------------------
-def _write_grid(tmp_path, monkeypatch, grid):
-    """logs/<cfg name>/occupancy_grid.pt under a temporary working directory."""
-    from src.config.config import args
-    monkeypatch.chdir(tmp_path)
-    d = tmp_path / "logs" / os.path.splitext(os.path.basename(args.cfg_file))[0]
-    d.mkdir(parents=True)
-    torch.save(grid, str(d / "occupancy_grid.pt"))
-
-
 def test_training_step_accelerated(g2, mg, cuda, trained, trained_grid, tmp_path, monkeypatch):
     from src.train.optimizer import make_optimizer
     from src.train.trainers.make_trainer import make_trainer

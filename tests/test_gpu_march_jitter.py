@@ -22,66 +22,22 @@ import numpy as np
 import pytest
 import torch
 
+from march_support import (MAPS, _batch, _flat_grad, _loss, _march_grad, _trained_net, _trainer, _write_grid,
+                           fixture_net, fp32_cfg, g2, lego_grid, trained_grid)
+
 pytestmark = pytest.mark.gpu
 
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
-HERE = os.path.dirname(os.path.abspath(__file__))
-MAPS = ("rgb_map_f", "depth_map_f", "acc_map_f")
 STEP = np.float32(0.005)
 BELOW_STEP = np.nextafter(STEP, np.float32(0))  # the largest shift below a step
 GROUP_SHIFTS = [np.float32(0), np.float32(0.00125), np.float32(0.0025), BELOW_STEP]
 
 
-@pytest.fixture(scope="module")
-def g2():
-    return np.load(os.path.join(HERE, "golden", "golden_v2.npz"), allow_pickle=False)
-
-
-@pytest.fixture(scope="module")
-def lego_grid():
-    z = np.load(os.path.join(HERE, "golden", "lego_occupancy_grid.npz"))
-    shape = tuple(int(v) for v in z["shape"])
-    return torch.from_numpy(np.unpackbits(z["packed"])[: int(np.prod(shape))].reshape(shape).astype(bool))
-
-
-@pytest.fixture(scope="module")
-def trained_grid(g2):
-    return torch.from_numpy(np.unpackbits(g2["bake128_packed"])[: 128 ** 3].reshape(128, 128, 128).astype(bool))
-
-
 @pytest.fixture()
 def jcfg():
     """cfg with the keys the tests below set restored afterwards."""
-    from src.config import cfg
-    ta = cfg.task_arg
-    keys = ("train_renderer", "train_grid", "train_march_jitter", "point_budget", "mlp_dtype", "perturb",
-            "chunk_size")
-    old = {k: ta[k] for k in keys if k in ta}
-    ta.perturb = 0
-    ta.mlp_dtype = "fp32"
-    yield cfg
-    for k in keys:
-        if k in old:
-            ta[k] = old[k]
-        else:
-            ta.pop(k, None)
-
-
-def _trained_net(cuda):
-    from src.models.nerf.network import Network
-    z = np.load(os.path.join(HERE, "golden", "trained_v2.npz"), allow_pickle=False)
-    torch.manual_seed(0)
-    net = Network()
-    net.load_state_dict({k: torch.from_numpy(z[k]) for k in z.files}, strict=True)
-    return net.to(cuda)
-
-
-def _batch(rays, cuda, rgbs=None):
-    b = {"rays": torch.as_tensor(rays).to(cuda)[None], "near": torch.tensor([2.0], device=cuda),
-         "far": torch.tensor([6.0], device=cuda)}
-    if rgbs is not None:
-        b["rgbs"] = torch.as_tensor(rgbs).to(cuda)[None]
-    return b
+    yield from fp32_cfg(("train_renderer", "train_grid", "train_march_jitter", "point_budget", "mlp_dtype",
+                         "perturb", "chunk_size"))
 
 
 def _random_shifts(n, seed):
@@ -214,24 +170,6 @@ def test_shifted_walk_against_brute_force(cuda, walk_cases, name, use_macro):
 # --------------------------------------------------------------------------------------
 # 3. null, zeros, and groups
 # --------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def fixture_net(cuda, g2, trained_grid):
-    """The trained fixture net, its optimizer (the flat gradient), the 256 march rays, a ground truth."""
-    from src.config import cfg
-    from src.train.optimizer import make_optimizer
-    old = {k: cfg.task_arg[k] for k in ("perturb", "mlp_dtype")}
-    cfg.task_arg.perturb = 0
-    cfg.task_arg.mlp_dtype = "fp32"
-    net = _trained_net(cuda)
-    opt = make_optimizer(cfg, net)
-    rays = torch.from_numpy(g2["march_rays"]).to(cuda)
-    t_table = torch.from_numpy(g2["march_t_table"]).to(cuda)
-    gt = torch.rand(256, 3, generator=torch.Generator().manual_seed(1)).to(cuda)
-    yield {"net": net, "opt": opt, "rays": rays, "t_table": t_table, "gt": gt, "grid": trained_grid.to(cuda)}
-    for k, v in old.items():
-        cfg.task_arg[k] = v
-
-
 def _march(f, rays, grid=None, **kw):
     from nerf_amd import ops
     kw.setdefault("t_table", f["t_table"])
@@ -403,26 +341,6 @@ def test_shifted_segment_kernels_against_fp64(cuda, white):
 # --------------------------------------------------------------------------------------
 # 5. the gradient end to end
 # --------------------------------------------------------------------------------------
-def _loss(out, gt, rows=None):
-    rgb, depth, acc = (out[m] if rows is None else out[m][:rows] for m in MAPS)
-    gt = gt if rows is None else gt[:rows]
-    return torch.nn.functional.mse_loss(rgb, gt) + 0.1 * depth.mean() + 0.1 * acc.mean()
-
-
-def _flat_grad(f, loss):
-    from nerf_amd import ops
-    f["opt"].zero_grad()
-    with ops.direct_grad():
-        loss.backward()
-    return f["opt"].flat_grad.clone()
-
-
-def _march_grad(f, rays, dtype, **kw):
-    from nerf_amd import ops
-    kw.setdefault("t_table", f["t_table"])
-    return ops.march_grad(f["net"].model_fine.packer(), rays, 2.0, 6.0, f["grid"], dtype=dtype, **kw)
-
-
 @pytest.mark.parametrize("dtype", ["fp32", "bf16x3f"])
 def test_gradient_with_one_shift_equals_the_shifted_table(cuda, fixture_net, dtype):
     f = fixture_net
@@ -488,22 +406,6 @@ def test_budget_cuts_the_shift_with_the_rays(cuda, fixture_net):
 # --------------------------------------------------------------------------------------
 # 7. the trainer
 # --------------------------------------------------------------------------------------
-def _write_grid(tmp_path, monkeypatch, grid):
-    """logs/<cfg name>/occupancy_grid.pt under a temporary working directory."""
-    from src.config.config import args
-    monkeypatch.chdir(tmp_path)
-    d = tmp_path / "logs" / os.path.splitext(os.path.basename(args.cfg_file))[0]
-    d.mkdir(parents=True)
-    torch.save(grid, str(d / "occupancy_grid.pt"))
-
-
-def _trainer(cfg, cuda):
-    from src.train.optimizer import make_optimizer
-    from src.train.trainers.make_trainer import make_trainer
-    net = _trained_net(cuda)  # (torch.manual_seed(0): the renderer's seed follows torch.initial_seed())
-    return net, make_trainer(cfg, net), make_optimizer(cfg, net)
-
-
 def test_trainer_with_jitter(cuda, jcfg, g2, trained_grid, tmp_path, monkeypatch):
     cfg = jcfg
     ta = cfg.task_arg

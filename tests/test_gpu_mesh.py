@@ -16,6 +16,8 @@ import torch
 
 import mesh_numpy as M
 
+from march_support import trained_state
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(os.path.dirname(HERE), "nerf-replication_amd")
@@ -176,12 +178,6 @@ def test_bad_fields_raise(cuda):
 # the trained fixture net: field, mesh, PLY, entry point
 # ---------------------------------------------------------------------------------------------
 N_NET = 48
-
-
-@pytest.fixture(scope="module")
-def trained_state():
-    z = np.load(os.path.join(HERE, "golden", "trained_v2.npz"), allow_pickle=False)
-    return {k: torch.from_numpy(z[k]) for k in z.files}
 
 
 @pytest.fixture(scope="module")

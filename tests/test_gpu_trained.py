@@ -34,6 +34,8 @@ import numpy as np
 import pytest
 import torch
 
+from march_support import g2, trained_state
+
 pytestmark = pytest.mark.gpu
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,17 +55,6 @@ BF16_GRAD_L2 = {"grad64": 0.5, "grad4096": 0.15}
 # entry error 3.6e-3 / 2.9e-3 of the tensor's largest, relative L2 2.1e-3 / 9.4e-4 for 64 / 4096
 # rays -- 200-350x closer than the bf16 tier's 0.74 / 0.31)
 BF16X3F_GRAD_L2 = {"grad64": 4e-3, "grad4096": 2e-3}
-
-
-@pytest.fixture(scope="module")
-def g2():
-    return np.load(os.path.join(HERE, "golden", "golden_v2.npz"), allow_pickle=False)
-
-
-@pytest.fixture(scope="module")
-def trained_state():
-    z = np.load(os.path.join(HERE, "golden", "trained_v2.npz"), allow_pickle=False)
-    return {k: torch.from_numpy(z[k]) for k in z.files}
 
 
 def state_sha256(state):

@@ -9,33 +9,20 @@ import re
 import pytest
 import torch
 
+from march_support import lib, restored_keys
+
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("nerf_grid_update_points", "nerf_grid_update_apply", "nerf_grid_update_threshold")
 LEGO = ((-1.5, -1.5, -1.5), (1.5, 1.5, 1.5))
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from nerf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("library not built (run __graft_entry__.build())")
-    return _lib.lib()
-
-
 @pytest.fixture()
 def task_arg():
     """cfg.task_arg with the keys this file touches restored afterwards."""
     from src.config import cfg
-    ta = cfg.task_arg
-    keys = ("train_renderer", "train_grid", "grid_update")
-    old = {k: ta[k] for k in keys if k in ta}
-    yield ta
-    for k in keys:
-        if k in old:
-            ta[k] = old[k]
-        else:
-            ta.pop(k, None)
+    with restored_keys(cfg.task_arg, ("train_renderer", "train_grid", "grid_update")) as ta:
+        yield ta
 
 
 # --------------------------------------------------------------------------------------

@@ -9,22 +9,12 @@ import re
 import numpy as np
 import pytest
 
+from march_support import _declared, blend_f32, built_lib as lib, restored_keys
+
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEY = "train_background"
 FWD, BWD, RAYGEN = "nerf_march_seg_composite_fwd_bg", "nerf_march_seg_composite_bwd_bg", "nerf_raygen_rgba"
-
-
-def _declared(text, name):
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, f"{name} is not declared"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from nerf_amd import _lib
-    return _lib.lib()  # (raises when the library is not built)
 
 
 def test_header_and_signature_table_have_the_three_symbols(lib):
@@ -153,15 +143,8 @@ def test_ops_check_the_colours_before_the_device():
 @pytest.fixture()
 def task_arg():
     from src.config import cfg
-    ta = cfg.task_arg
-    keys = ("train_renderer", "train_grid", KEY)
-    old = {k: ta[k] for k in keys if k in ta}
-    yield ta
-    for k in keys:
-        if k in old:
-            ta[k] = old[k]
-        else:
-            ta.pop(k, None)
+    with restored_keys(cfg.task_arg, ("train_renderer", "train_grid", "train_background")) as ta:
+        yield ta
 
 
 def test_config_key_default_and_validation(task_arg, tmp_path, monkeypatch):
@@ -245,16 +228,6 @@ def _rgba_fixture():
     px[8:, :, 3] = rng.integers(1, 255, (8, 16), dtype=np.uint8)
     assert (px[..., 3] == 0).any() and (px[..., 3] == 255).any() and ((px[..., 3] > 0) & (px[..., 3] < 255)).any()
     return px
-
-
-def blend_f32(rgba, bg):
-    """The kernel's blend in numpy: fadd(fmul(C, a), fmul(fsub(1, a), bg)), every op rounded to fp32."""
-    rgba, bg = np.asarray(rgba, np.float32), np.asarray(bg, np.float32)
-    a = rgba[..., 3:4]
-    left = (np.float32(1.0) - a).astype(np.float32)
-    out = ((rgba[..., :3] * a).astype(np.float32) + (left * bg).astype(np.float32)).astype(np.float32)
-    assert out.dtype == np.float32
-    return out
 
 
 def test_white_composite_identity():

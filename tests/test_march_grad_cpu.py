@@ -9,29 +9,13 @@ import numpy as np
 import pytest
 import torch
 
+from march_support import g2, lib, mg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
 NEW = ("nerf_march_composite_used", "nerf_march_segments", "nerf_march_seg_composite_fwd",
        "nerf_march_seg_composite_bwd")
 TAGS = ("mg_rgb", "mg_all")
-
-
-@pytest.fixture(scope="module")
-def mg():
-    return np.load(os.path.join(HERE, "golden", "golden_march_grad.npz"), allow_pickle=False)
-
-
-@pytest.fixture(scope="module")
-def g2():
-    return np.load(os.path.join(HERE, "golden", "golden_v2.npz"), allow_pickle=False)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from nerf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("library not built (run __graft_entry__.build())")
-    return _lib.lib()
 
 
 def test_fixture_keys_and_shapes(mg):

@@ -7,6 +7,8 @@ import re
 
 import pytest
 
+from march_support import _declared, built_lib as lib, restored_keys
+
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -18,18 +20,6 @@ SHIFTED = {
     "nerf_march_seg_composite_fwd_shift": "nerf_march_seg_composite_fwd",
     "nerf_march_seg_composite_bwd_shift": "nerf_march_seg_composite_bwd",
 }
-
-
-def _declared(text, name):
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, f"{name} is not declared"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from nerf_amd import _lib
-    return _lib.lib()  # (raises when the library is not built)
 
 
 def test_header_and_signature_table_have_the_six_symbols(lib):
@@ -86,15 +76,8 @@ def test_t_shift_is_checked_before_the_device():
 @pytest.fixture()
 def task_arg():
     from src.config import cfg
-    ta = cfg.task_arg
-    keys = ("train_renderer", "train_grid", "train_march_jitter")
-    old = {k: ta[k] for k in keys if k in ta}
-    yield ta
-    for k in keys:
-        if k in old:
-            ta[k] = old[k]
-        else:
-            ta.pop(k, None)
+    with restored_keys(cfg.task_arg, ("train_renderer", "train_grid", "train_march_jitter")) as ta:
+        yield ta
 
 
 def test_config_key_default_and_validation(task_arg, tmp_path, monkeypatch):

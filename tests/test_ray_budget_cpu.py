@@ -9,6 +9,8 @@ import re
 
 import pytest
 
+from march_support import lib, restored_keys
+
 os.environ.setdefault("NERF_AMD_NO_ARGV", "1")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULTS = {"target": 0, "max_points": 0, "min_rays": 1024, "max_rays": 32768, "granularity": 256}
@@ -27,15 +29,9 @@ def formula(n_rays, n_queried, target, min_rays=1024, max_rays=32768, granularit
 def task_arg():
     """cfg.task_arg with the keys this file touches restored afterwards."""
     from src.config import cfg
-    ta = cfg.task_arg
     keys = ("train_renderer", "train_grid", "grid_update", "point_budget", "train_rays")
-    old = {k: ta[k] for k in keys if k in ta}
-    yield ta
-    for k in keys:
-        if k in old:
-            ta[k] = old[k]
-        else:
-            ta.pop(k, None)
+    with restored_keys(cfg.task_arg, keys) as ta:
+        yield ta
 
 
 # --------------------------------------------------------------------------------------
@@ -210,14 +206,6 @@ def test_the_module_needs_no_torch():
 # --------------------------------------------------------------------------------------
 # C ABI
 # --------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    from nerf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("library not built (run __graft_entry__.build())")
-    return _lib.lib()
-
-
 def test_header_and_signature_have_the_entry_point(lib):
     from nerf_amd import _lib
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "nerf_amd.h")).read(), flags=re.S)
