@@ -788,6 +788,38 @@ def test_mlp_ragged_sizes_row_independent(cuda, ops, seeded_state, dtype):
             assert torch.equal(got, ref[:m]), (dtype, m)
 
 
+@pytest.mark.parametrize("dtype", ["fp32", "bf16", "bf16x3"])
+def test_mlp_rows_independent_of_position(cuda, ops, seeded_state, dtype):
+    """A sample's raw output does not depend on its position in the launch: 4,133 points evaluated as they are
+    and through a random permutation of the rows (dir_index permuted along) give the same bits after
+    un-permuting, through ops.mlp and through ops.mlp_count (the count read on the device).  The round march
+    relies on it: a round's buffer holds a ray's points wherever the reservation put them
+    (test_gpu_march_rounds.py::test_ops_march_round_options_change_no_bit)."""
+    g = torch.Generator().manual_seed(41)
+    M, ndir = 4133, 97
+    pts = (torch.rand(M, 3, generator=g) * 3 - 1.5).to(cuda)
+    vd = torch.nn.functional.normalize(torch.randn(ndir, 3, generator=g), dim=-1).to(cuda)
+    di = torch.randint(0, ndir, (M,), generator=g, dtype=torch.int32).to(cuda)
+    perm = torch.randperm(M, generator=g).to(cuda)
+    assert not torch.equal(perm, torch.arange(M, device=cuda))
+    p_pts, p_di = pts[perm].contiguous(), di[perm].contiguous()
+    packer = ops.PackedMLP([seeded_state[f"model.{n}"].to(cuda) for n in ops.NET_PARAM_NAMES])
+    count = torch.tensor([M, 0], dtype=torch.int32, device=cuda)
+
+    def unpermute(raw):
+        out = torch.empty_like(raw)
+        out[perm] = raw
+        return out
+
+    with torch.no_grad():
+        ref = ops.mlp(packer, pts, vd, 1, di, dtype)
+        assert torch.equal(unpermute(ops.mlp(packer, p_pts, vd, 1, p_di, dtype)), ref), dtype
+        ref = ops.mlp_count(packer, pts, vd, di, count, torch.full((M, 4), float("nan"), device=cuda), dtype)
+        assert not bool(torch.isnan(ref).any())
+        raw = ops.mlp_count(packer, p_pts, vd, p_di, count, torch.full((M, 4), float("nan"), device=cuda), dtype)
+        assert torch.equal(unpermute(raw), ref), dtype
+
+
 @pytest.mark.parametrize("dtype", ["fp32", "bf16", "bf16x3", "bf16x3f", "bf16x6"])
 def test_pack_plan_gather_matches_direct_pack(cuda, ops, seeded_state, dtype):
     """nerf_mlp_pack gathers through its cached pack plan when the 24 parameters lie back to back
